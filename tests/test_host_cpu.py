@@ -420,15 +420,18 @@ def test_divergence_guard_decision_is_collective_gloo_world2(tmp_path):
     assert all("OK" in o for o in outs)
 
 
-def test_bench_gpus4_code_path_dry_run_gloo_world4():
+def test_bench_gpus4_code_path_dry_run_gloo_world4(tmp_path):
     """`python bench.py --gpus 4` end to end on CPU (PCRL_BENCH_DRYRUN=1): the self-spawn through torch.distributed.run, four gloo
     ranks, the rank / device table, the four-setting bucket A/B, the barrier-bracketed timed region, the JSON line -- with the step replaced by a
-    stub whose KNOWN gradients go through the engine's parking / bucket / all-reduce machinery and are checked after every optimizer step."""
+    stub whose KNOWN gradients go through the engine's parking / bucket / all-reduce machinery and are checked after every optimizer step.
+    A plain run (no --full) carries no per-kernel figures; --dump-outputs writes the last step's losses from rank 0."""
     import json
+    import numpy as np
     env = dict(os.environ, PCRL_BENCH_DRYRUN="1", PCRL_BIND_CPUS="0")
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "4", "--warmup", "1"], env=env, stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, text=True, timeout=600)
+    dump = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "4", "--warmup", "1", "--dump-outputs", str(dump)], env=env,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert lines and lines[-1].startswith("{"), r.stdout[-500:]        # the JSON line is the LAST line of stdout
@@ -443,6 +446,10 @@ def test_bench_gpus4_code_path_dry_run_gloo_world4():
     assert abs(d["per_gpu_value"] * 4 - d["value"]) < 0.02 * d["value"]
     assert d["dry_run"]["gradient_checks_passed"] >= 4 + 1 + 4 * 8 and "DRY RUN" in d["config"]["workload"]
     assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert not {"roofline", "kernels", "diag", "secondary", "cpu_baseline"} & set(d)
+    for name in ("loss", "loss1", "loss2", "loss4", "local_loss"):
+        assert np.load(dump / (name + ".npy")).dtype == np.float32
+    assert round(float(np.load(dump / "loss.npy")), 5) == d["final_loss"]
 
 
 def test_bnr_counted_wait_matches_the_stores_behind_the_dma_pieces(tmp_path):

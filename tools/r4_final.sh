@@ -3,13 +3,14 @@
 TAG=${1:-r04z}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
+O=${OUT_DIR:-out}; mkdir -p "$O"      # the bench lines of this script
 python -m pytest tests -q -m gpu > gpurun_out/${TAG}_pytest_gpu.log 2>&1
 grep -E "passed|failed" gpurun_out/${TAG}_pytest_gpu.log | tail -1
-python bench.py --steps 20 --warmup 5 > gpurun_out/${TAG}_bench_driver.json 2> gpurun_out/${TAG}_bench_driver.err
-python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench_driver.json 2> $O/${TAG}_bench_driver.err
+python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 python - <<PY
 import json
-for f in ("gpurun_out/${TAG}_bench_driver.json", "gpurun_out/${TAG}_bench.json"):
+for f in ("$O/${TAG}_bench_driver.json", "$O/${TAG}_bench.json"):
     d = json.loads(open(f).read().strip().splitlines()[-1])
     print(f, d["value"], d["ms_per_step"], d["roofline"]["frac"], d["step_mfma_frac"], d["step_mfma_frac_executed"], {k: (v.get("value"), v.get("ms_per_step")) for k, v in d["secondary"].items()})
 PY

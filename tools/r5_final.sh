@@ -4,12 +4,13 @@
 TAG=${1:-r05bd}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
+O=${OUT_DIR:-out}; mkdir -p "$O"      # the bench lines of this script
 python -m pytest tests -q -m gpu > gpurun_out/${TAG}_pytest_gpu.log 2>&1
 grep -E "passed|failed" gpurun_out/${TAG}_pytest_gpu.log | tail -1
-python bench.py --steps 20 --warmup 5 > gpurun_out/${TAG}_bench_driver.json 2> gpurun_out/${TAG}_bench_driver.err
+python bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench_driver.json 2> $O/${TAG}_bench_driver.err
 python - <<PY
 import json
-d = json.loads(open("gpurun_out/${TAG}_bench_driver.json").read().strip().splitlines()[-1])
+d = json.loads(open("$O/${TAG}_bench_driver.json").read().strip().splitlines()[-1])
 print(d["value"], d["ms_per_step"], d["roofline"]["kernel"], d["roofline"]["frac"], d["roofline"].get("weighted_matrix_frac"), d["step_mfma_frac"], d["step_mfma_frac_executed"], {k: (v.get("value"), v.get("ms_per_step")) for k, v in d["secondary"].items()})
 PY
 bash tools/profile_step.sh ${TAG} > gpurun_out/${TAG}_profile_step.log 2>&1
