@@ -500,6 +500,27 @@ int pcrl_aug_znorm(const float* x, float* y, const float* mean, const float* rst
 int pcrl_aug_swap(float* x, const int* origins, int B, int D, int H, int W, int pd, int ph, int pw, int iters, pcrl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * 2D (chest X-ray) input pipeline: the torchvision chain of data.py:14-61 / datasets/chestDataset.py:31-48 on uint8 images, restating
+ * the Pillow arithmetic every one of its transforms hands over to (csrc/augment2d.hip).  V views of side S (224 global, 96 local), one
+ * record of PCRL_AUG2D_NPARAM int32 per view (drawn and packed by pcrlv2_amd/data_chest.py):
+ *   [0] byte offset of the view's source in `src` (H x W x C interleaved uint8, C = 1 for a mode-L image, 3 otherwise), [1..3] H, W, C,
+ *   [4..7] crop box j, i, w, h (RandomResizedCrop), [8..13] NEAREST rotation as Pillow's 16.16 fixed-point affine a0..a5 (RandomRotation),
+ *   [14] flip (RandomHorizontalFlip), [15] grayscale (RandomGrayscale), [16] blur, [17] integer box radius, [18] ww, [19] fw (Pillow's
+ *   BoxBlur weights of GaussianBlur(sigma)), [20] number of ColorJitter ops, [21] their order (4 bits each: 0 brightness, 1 contrast,
+ *   2 saturation, 3 hue), [22..24] brightness / contrast / saturation factors as float32 bits, [25] hue shift (0..255 added to PIL's H),
+ *   [26] Cutout holes, [27..38] up to three clipped holes (y0, y1, x0, x1), [39] byte offset of the view's intermediate in `inter`.
+ *   hresample   : horizontal BILINEAR pass of the crop box: inter = [h][S][C] uint8 (max_rows = the largest h)  -- transforms.RandomResizedCrop
+ *   spatial     : vertical pass at the pixel the rotation and the flip pick: view = [V][3][S][S] uint8 (C planes used), target = NULL or
+ *                 [V][3][S][S] float32 Normalize(ToTensor(view))  -- RandomResizedCrop + RandomRotation + RandomHorizontalFlip,
+ *                 chestDataset.py:36-41 (x, x2)
+ *   photometric : grayscale, blur, jitter, ToTensor, Normalize, Cutout of the views: out = [V][3][S][S] float32, u8_out = NULL or the
+ *                 uint8 planes before ToTensor (tests)  -- data.py:31-44 (train_transform, local_transform), utils.py:60-98 (Cutout) */
+#define PCRL_AUG2D_NPARAM 40
+int pcrl_aug2d_hresample(const uint8_t* src, const int* params, uint8_t* inter, int V, int S, int max_rows, pcrl_stream_t stream);
+int pcrl_aug2d_spatial(const uint8_t* inter, const int* params, uint8_t* view, float* target, int V, int S, pcrl_stream_t stream);
+int pcrl_aug2d_photometric(const uint8_t* view, const int* params, float* out, uint8_t* u8_out, int V, int S, pcrl_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Test hooks (NOT part of the drop-in surface; process-wide atomics, default 0 / tr 1 = the product path).  They select which
  * of the kernels behind one entry point runs, so that tests can check every kernel against the same reference and probes can
  * time them against each other inside one process (tools/conv_probe.py).

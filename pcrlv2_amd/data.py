@@ -305,25 +305,48 @@ def worker_affinity_init(worker_id: int):
         pass
 
 
+class LunaKind:
+    """What AugmentedLoader needs to know about the LUNA pre-task samples: the slot buffers (one raw crop pair + its locals per row), the
+    datasets that fill them, and the device augmentation.  pcrlv2_amd/data_chest.ChestKind is the 2D counterpart."""
+
+    def __init__(self, files):
+        self.pshape = tuple(np.load(files[0], mmap_mode="r").shape)
+        self.lshape = tuple(np.load(files[0].replace("global", "local"), mmap_mode="r").shape)
+
+    def slot_shapes(self):
+        return [(self.pshape, torch.float32), (self.lshape, torch.float32)]
+
+    def slot_dataset(self, files, bufs):
+        return _SlotCrops(files, *bufs)
+
+    def dataset(self, files):
+        return LunaCropPairs(files)
+
+    def augment(self, device, seed):
+        return GpuLunaAugment(device, seed)
+
+
 class AugmentedLoader:
-    """DataLoader over raw crops + GpuLunaAugment: iterates batches with the contract of datasets/lunaDataset.py:79-81.
+    """DataLoader over raw samples + a device augmentation (GpuLunaAugment by default; `kind` names the dataset and the augmentation, see
+    LunaKind): iterates batches with the contract of datasets/lunaDataset.py:79-81.
 
     One batch ahead: the host-to-device copy and the augmentation kernels of batch k + 1 are enqueued on their OWN stream BEFORE batch k is handed
     to the training loop, so they run under step k (~1.4 ms of HBM-bound kernels per b = 32 batch next to a ~31 ms step) instead of in
     front of step k + 1 on its critical chain; the consumer's stream waits for the batch's event when it receives it.  The reference's
     workers do the same job one batch ahead on the CPU (DataLoader prefetching, data.py:90-93)."""
 
-    def __init__(self, files, batch_size, workers, device, shuffle=True, seed=0, drop_last=False):
+    def __init__(self, files, batch_size, workers, device, shuffle=True, seed=0, drop_last=False, kind=None):
         cuda = torch.device(device).type == "cuda"
         self.slots = None
         files = list(files)
         use_slots = cuda and PIN_MODE == "slots" and AUG_STREAM and workers > 0 and len(files) > 0
+        if kind is None:
+            kind = LunaKind(files) if use_slots else None
         if use_slots:
             prefetch = 2
             nslots = prefetch * workers + 6            # outstanding index batches + the batches this process still holds (see __iter__)
-            pshape = tuple(np.load(files[0], mmap_mode="r").shape)
-            lshape = tuple(np.load(files[0].replace("global", "local"), mmap_mode="r").shape)
-            need = 4 * nslots * batch_size * (int(np.prod(pshape)) + int(np.prod(lshape)))
+            shapes = kind.slot_shapes()
+            need = sum(torch.empty((), dtype=dt).element_size() * nslots * batch_size * int(np.prod(sh)) for sh, dt in shapes)
             try:        # the slots live in /dev/shm: a container with a small shm mount would die with SIGBUS on the first write, not with an exception
                 vfs = os.statvfs("/dev/shm")
                 use_slots = vfs.f_bavail * vfs.f_frsize > 1.25 * need
@@ -334,23 +357,22 @@ class AugmentedLoader:
         if use_slots:
             # zero-filled right after share_memory_(): the pages are COMMITTED now, so the /dev/shm room check of the next loader / rank sees real
             # usage instead of passing on sparse files and dying with SIGBUS later
-            pair_buf = torch.empty((nslots, batch_size) + pshape, dtype=torch.float32).share_memory_().zero_()
-            local_buf = torch.empty((nslots, batch_size) + lshape, dtype=torch.float32).share_memory_().zero_()
-            pinned = _pin_registered(pair_buf) and _pin_registered(local_buf)
+            bufs = [torch.empty((nslots, batch_size) + tuple(sh), dtype=dt).share_memory_().zero_() for sh, dt in shapes]
+            pinned = all(_pin_registered(t) for t in bufs)
             if not pinned:
                 # the copies out of pageable shared memory would be synchronous staged copies: the 841 -> 1015 crops/s of the slot loader is gone
                 print("[pcrlv2_amd.data] warning: hipHostRegister refused the shared batch slots (locked-memory limit?): host-to-device copies are "
                       "staged and synchronous -- expect the loader to fall behind the step (PCRL_LOADER_PIN=ring copies into pinned buffers instead)", flush=True)
-            self.slots = (pair_buf, local_buf, pinned)
-            self.loader = torch.utils.data.DataLoader(_SlotCrops(files, pair_buf, local_buf), num_workers=workers, collate_fn=lambda items: (items[0][0], len(items)),
+            self.slots = tuple(bufs) + (pinned,)
+            self.loader = torch.utils.data.DataLoader(kind.slot_dataset(files, bufs), num_workers=workers, collate_fn=lambda items: (items[0][0], len(items)),
                                                       batch_sampler=_SlotBatches(len(files), batch_size, shuffle, drop_last, nslots, seed),
                                                       persistent_workers=True, prefetch_factor=prefetch, worker_init_fn=worker_affinity_init)
         else:
-            self.loader = torch.utils.data.DataLoader(LunaCropPairs(files), batch_size=batch_size, shuffle=shuffle, num_workers=workers,
+            self.loader = torch.utils.data.DataLoader(kind.dataset(files) if kind is not None else LunaCropPairs(files), batch_size=batch_size, shuffle=shuffle, num_workers=workers,
                                                       pin_memory=cuda and PIN_MODE in ("loader", "slots"), drop_last=drop_last,
                                                       persistent_workers=workers > 0, prefetch_factor=4 if workers > 0 else None,
                                                       worker_init_fn=worker_affinity_init if workers > 0 else None)
-        self.augment = GpuLunaAugment(device, seed)
+        self.augment = kind.augment(device, seed) if kind is not None else GpuLunaAugment(device, seed)
         self._stream = None
         self._ring, self._ring_pos = None, 0
         self._events = []
@@ -401,8 +423,8 @@ class AugmentedLoader:
         self._events = []
         if self.slots is not None:
             self.loader = None          # the iterator and its persistent workers go first
-        if self.slots is not None and self.slots[2]:
-            for t in self.slots[:2]:
+        if self.slots is not None and self.slots[-1]:
+            for t in self.slots[:-1]:
                 try:
                     torch.cuda.cudart().cudaHostUnregister(t.data_ptr())
                 except Exception:
@@ -418,8 +440,8 @@ class AugmentedLoader:
     def __iter__(self):
         import time
         if not AUG_STREAM:
-            for pair, local in self.loader:
-                yield self.augment(pair, local)
+            for item in self.loader:
+                yield self.augment(*item)
             return
         dev = self.augment.device
         if self._stream is None:
@@ -444,12 +466,12 @@ class AugmentedLoader:
                 sl, rows = item
                 if len(self._events) >= 3:
                     self._events[-3].synchronize()
-                pair, local, slot = self.slots[0][sl, :rows], self.slots[1][sl, :rows], None
+                parts, slot = tuple(t[sl, :rows] for t in self.slots[:-1]), None
             else:
-                pair, local, slot = self._stage(*item)
+                *parts, slot = self._stage(*item)
             t2 = time.perf_counter()
             with torch.cuda.stream(self._stream):
-                batch = self.augment(pair, local)
+                batch = self.augment(*parts)
                 ev = torch.cuda.Event()
                 ev.record(self._stream)
                 if slot is not None:

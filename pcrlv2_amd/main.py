@@ -6,10 +6,11 @@
 Differences from the reference: `--gpus` selects the visible devices exactly as before, but multi-GPU runs use one
 process per GPU (RCCL) instead of nn.DataParallel -- with a plain `python main.py` and several ids in --gpus the script
 re-launches itself under torch.distributed.run.  `--momentum/--weight_decay` are parsed as floats.  `--d 2` runs the 2D
-ResNet-18 U-Net path (pcrlv2_amd/train_2d.py; no segmentation_models_pytorch / torchvision needed) on `--data synthetic` only:
-the chest X-ray input pipeline is not part of this engine.  `--data synthetic` trains on generated batches of the reference's
-shapes (no dataset on disk needed); a LUNA pre-task directory is read by pcrlv2_amd/data.py (crops from disk, the reference's
-torchio augmentations restated on the GPU -- parity with torchio unpinned).
+ResNet-18 U-Net path (pcrlv2_amd/train_2d.py; no segmentation_models_pytorch / torchvision needed).  `--data synthetic` trains on
+generated batches of the reference's shapes (no dataset on disk needed); a LUNA pre-task directory is read by pcrlv2_amd/data.py
+(crops from disk, the reference's torchio augmentations restated on the GPU -- parity with torchio unpinned); with `--d 2` an image
+directory is read by pcrlv2_amd/data_chest.py (PNGs decoded by the workers, the reference's torchvision chain restated on the GPU at
+Pillow's arithmetic; the list is ./train_val_txt/chest_train.txt when it exists, otherwise every *.png under --data).
 """
 import argparse
 import os
@@ -105,16 +106,21 @@ class SyntheticChestLoader(SyntheticLunaLoader):
 
 
 def get_dataloader(args):
-    """`DataGenerator(args).pcrlv2_luna_pretask()` of the reference (data.py:63-99) -- `--data synthetic`: generated batches."""
+    """`DataGenerator(args).pcrlv2_luna_pretask()` / `.pcrlv2_chest_pretask()` of the reference (data.py:63-99 / 14-61) -- `--data synthetic`:
+    generated batches."""
     if args.data == 'synthetic' and args.d == 2:
         return {'train': SyntheticChestLoader(args.b, args.steps_per_epoch, args.size2d, args.seed + int(os.environ.get("RANK", "0"))), 'eval': None}
     if args.data == 'synthetic':
         return {'train': SyntheticLunaLoader(args.b, args.steps_per_epoch, args.seed + int(os.environ.get("RANK", "0"))), 'eval': None}
+    if args.d == 2 and os.path.isdir(args.data):
+        from .data_chest import chest_pretask_loaders     # images from disk, the torchvision chain on the GPU (data.py:14-61)
+        return chest_pretask_loaders(args)
     if args.n == 'luna' and os.path.isdir(os.path.join(args.data, 'subset0')):
         from .data import luna_pretask_loaders     # raw .npy crops from disk, augmentations on the GPU (pcrlv2_amd/data.py)
         return luna_pretask_loaders(args)
-    raise SystemExit("--data must be 'synthetic' or a LUNA pre-task directory (subset0..subset9 with <series>_global_<k>.npy / _local_<k>.npy, "
-                     "luna_preprocess.py:134-146).  The chest X-ray (2D) pipeline is not part of this engine.")
+    raise SystemExit("--data must be 'synthetic', a LUNA pre-task directory (subset0..subset9 with <series>_global_<k>.npy / _local_<k>.npy, "
+                     "luna_preprocess.py:134-146) or, with --d 2, a directory of chest X-ray images (listed in ./train_val_txt/chest_train.txt, "
+                     "or every *.png under it)")
 
 
 def main(argv=None):
