@@ -521,6 +521,32 @@ int pcrl_aug2d_spatial(const uint8_t* inter, const int* params, uint8_t* view, f
 int pcrl_aug2d_photometric(const uint8_t* view, const int* params, float* out, uint8_t* u8_out, int V, int S, pcrl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * LUNA16 pre-processing (luna_preprocess.py:134-348, csrc/luna_prep.hip, host side pcrlv2_amd/luna_prep.py).  Volumes are int16 in
+ * (z, y, x) memory order (GetArrayFromImage); the logical array is its transpose (x, y, z).  float64 arithmetic throughout.
+ *   resample : ITK ResampleImageFilter with an identity transform and output spacing 1: output index o has the continuous index
+ *              (o * 1.0) / spacing per axis, 0 unless it is < size - 0.5 on every axis; linear interpolation along x, then y, then z
+ *              (a + (b - a) * t, the upper neighbour clamped to size - 1); cast by clamping to the int16 range, truncating toward zero.
+ *              in = [Z][Y][X], out = [OZ][OY][OX].
+ *   windows  : W crop windows of `vol` ([Z][Y][X] int16, reads at z >= Z give the pad value -1000), each normalised
+ *              (clip to [-1000, 1000], (v + 1000) / 2000) and resized as skimage.transform.resize(order=1, mode='reflect',
+ *              preserve_range=True) does: separable Gaussian (mode mirror on the crop, scipy's symmetric correlate1d order) over the
+ *              axes with radius > 0, zoom with grid_mode coordinates (o + 0.5) * ratio - 0.5 and order-1 mirror weights, clip to the
+ *              crop's min / max.  One int64 record of PCRL_PREP_NREC per window:
+ *                [0..2] start x, y, z in the logical volume, [3..5] source sizes, [6..8] output sizes (z <= 64), [9..11] Gaussian radius
+ *                per axis (0: no filter, <= PCRL_PREP_RMAX), [12] offset of the window in `out` (doubles; stored [ox][oy][sd]), [13] sd:
+ *                output depths stored, [14] offset of its two workspace buffers in `ws` (doubles; 2 * sx*sy*sz), [15] depth-score
+ *                depth D (0: none; D + 2 <= oz).
+ *              One double record of PCRL_PREP_NPRM per window: [a * (RMAX + 1) + j] Gaussian weight of taps +-j on axis a,
+ *              [3 * (RMAX + 1) + a] zoom ratio in / out of axis a (host-computed).
+ *              stats = [W][3] int: the exact depth score 2 * n0 + n1 over d < D (k = the first of 0..2 with w[i,j,d+k] >= 0.425,
+ *              2 if none; n0 / n1 count k = 0 / 1), then the crop's raw min and max.  max_src / max_cols bound sx*sy*sz / ox*oy. */
+#define PCRL_PREP_NREC 16
+#define PCRL_PREP_NPRM 32
+#define PCRL_PREP_RMAX 8
+int pcrl_prep_resample(const int16_t* in, int16_t* out, int X, int Y, int Z, int OX, int OY, int OZ, double spacing_x, double spacing_y, double spacing_z, pcrl_stream_t stream);
+int pcrl_prep_windows(const int16_t* vol, int X, int Y, int Z, const int64_t* rec, const double* prm, int W, int64_t max_src, int max_cols, double* out, int64_t out_len, int* stats, double* ws, int64_t ws_len, pcrl_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Test hooks (NOT part of the drop-in surface; process-wide atomics, default 0 / tr 1 = the product path).  They select which
  * of the kernels behind one entry point runs, so that tests can check every kernel against the same reference and probes can
  * time them against each other inside one process (tools/conv_probe.py).

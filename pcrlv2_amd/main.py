@@ -118,8 +118,8 @@ def get_dataloader(args):
     if args.n == 'luna' and os.path.isdir(os.path.join(args.data, 'subset0')):
         from .data import luna_pretask_loaders     # raw .npy crops from disk, augmentations on the GPU (pcrlv2_amd/data.py)
         return luna_pretask_loaders(args)
-    raise SystemExit("--data must be 'synthetic', a LUNA pre-task directory (subset0..subset9 with <series>_global_<k>.npy / _local_<k>.npy, "
-                     "luna_preprocess.py:134-146) or, with --d 2, a directory of chest X-ray images (listed in ./train_val_txt/chest_train.txt, "
+    raise SystemExit("--data must be 'synthetic', a LUNA pre-task directory (subset0..subset9 with <series>_global_<k>.npy / _local_<k>.npy; "
+                     "make one from LUNA16 with `python luna_preprocess.py --data LUNA16 --save <dir>`) or, with --d 2, a directory of chest X-ray images (listed in ./train_val_txt/chest_train.txt, "
                      "or every *.png under it)")
 
 
