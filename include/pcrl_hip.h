@@ -79,6 +79,20 @@ int64_t pcrl_conv3d_k3_fwd_ws_bytes(int N, int D, int H, int W, int Ci, int Co, 
 int pcrl_conv3d_k3_fwd_ws(const void* x, const void* wp, const float* bias, void* y, float* stats_partial, void* ws, int64_t ws_bytes,
                           int N, int D, int H, int W, int Ci, int Co, int dtype, pcrl_stream_t stream);
 
+/* Inference forward of a LUConv in .eval() (models/pcrlv2_model_3d.py:9,12,21,33: aten::convolution -> aten::native_batch_norm on the running
+ * statistics -> aten::relu) as ONE pass: a[m][co] = act(scale[co] * (sum + bias[co]) + shift[co]) from the float32 accumulators, stored once in
+ * `dtype`.  No pre-normalisation tensor, no statistics rows.  x, wp: as pcrl_conv3d_k3_fwd; scale, shift: Co floats (eval-mode BatchNorm:
+ * gamma / sqrt(running_var + eps), beta - running_mean * scale); act: PCRL_ACT_RELU or PCRL_ACT_NONE (other codes are an error).
+ * Kernels: the wide-brick kernel where pcrl_conv3d_k3_fwd would take it, otherwise the gather kernel in one pass -- every shape is computed.
+ * `pcrl_conv3d_k3_fwd_affine_fused` (host only) -> 1 where this one pass replaces pcrl_conv3d_k3_fwd_ws + pcrl_bn_act_apply on the same kernel
+ * family (wide-brick shapes; gather shapes that are not split along K), 0 where the unfused convolution runs on a family without this
+ * epilogue (4x8x8 bricks, split-K, voxel-major rows) and the caller should keep the two passes.  `_ws_bytes` -> workspace size (0 today: every
+ * fused form is one pass; `ws` may be NULL). */
+int64_t pcrl_conv3d_k3_fwd_affine_fused(int N, int D, int H, int W, int Ci, int Co, int dtype);
+int64_t pcrl_conv3d_k3_fwd_affine_ws_bytes(int N, int D, int H, int W, int Ci, int Co, int dtype);
+int pcrl_conv3d_k3_fwd_affine(const void* x, const void* wp, const float* bias, const float* scale, const float* shift, void* a, void* ws,
+                              int64_t ws_bytes, int N, int D, int H, int W, int Ci, int Co, int act, int dtype, pcrl_stream_t stream);
+
 /* Data gradient of a 3x3x3 convolution (convolution_backward(input) of LUConv.conv1, models/pcrlv2_model_3d.py:9,33) WITH the first pass of the
  * BatchNorm backward of the layer BELOW in its epilogue -- for the case that layer's activation has this convolution as its only consumer
  * (ops.0 -> ops.1 inside nn.Sequential(LUConv, LUConv), :37-45): dx IS the gradient of a = relu(scale * bn_y + shift), and rows of
@@ -107,6 +121,11 @@ int pcrl_conv3d_k3_wgrad(const void* x, const void* dy, float* dw_ref, void* ws,
 int64_t pcrl_conv3d_k3_c1_stats_rows(int N, int D, int H, int W, int Co, int dtype);
 int pcrl_conv3d_k3_c1_fwd(const float* x, const float* w_ref, const float* bias, void* y, float* stats_partial,
                           int N, int D, int H, int W, int Co, int dtype, pcrl_stream_t stream);
+/* The first layer in .eval() (pcrlv2_model_3d.py:101 -> down_tr64.ops.0: convolution -> BatchNorm on the running statistics -> relu) as one
+ * pass, like pcrl_conv3d_k3_fwd_affine: a = act(scale[co] * (sum + bias[co]) + shift[co]), act = PCRL_ACT_RELU or PCRL_ACT_NONE; every shape
+ * and dtype pcrl_conv3d_k3_c1_fwd takes, on the same kernels. */
+int pcrl_conv3d_k3_c1_fwd_affine(const float* x, const float* w_ref, const float* bias, const float* scale, const float* shift, void* a,
+                                 int N, int D, int H, int W, int Co, int act, int dtype, pcrl_stream_t stream);
 size_t pcrl_conv3d_k3_c1_wgrad_ws_bytes(int N, int D, int H, int W, int Co);
 int pcrl_conv3d_k3_c1_wgrad(const float* x, const void* dy, float* dw_ref, void* ws, size_t ws_bytes,
                             int N, int D, int H, int W, int Co, int dtype, pcrl_stream_t stream);
@@ -269,6 +288,22 @@ int pcrl_mse_bwd(const float* p, const float* gt, const float* dloss, float* dp,
 int pcrl_cosine_mean_fwd(const float* x, const float* y, float* out, float* saved, int rows, int C, float eps, pcrl_stream_t stream);
 int pcrl_cosine_mean_bwd(const float* x, const float* y, const float* saved, const float* dout, float* dx,
                          int rows, int C, float eps, pcrl_stream_t stream);
+
+/* Validation metrics of one batch (the loss terms of train_3d.py:119-138 -- aten::mse_loss at :135,137, cos_loss :86-92 -- at EVERY scale index
+ * k = 0..2 instead of the drawn one), added to a device accumulator of 11 doubles as batch-size-weighted sums:
+ *   acc[0] += B MSE(out1, gt);  acc[1 + k] += B MSE(mask_k, gt);
+ *   acc[4 + k] += B * -(mean cos(pre1_k, pro2_k) + mean cos(pre2_k, pro1_k)) / 2                                     (cos_loss(.., view 1, view 2) at index k)
+ *   acc[7 + k] += B * mean over local views i and global views v of -(mean cos(pre_v, proL_i) + mean cos(preL_i, pro_v)) / 2      (train_3d.py:127-134)
+ *   acc[10] += B.
+ * out1, mask_k, gt: float32 [B * S] (S voxels per sample; the masks already upsampled); pro / pre of view 1 and 2 at scale k: float32 [B][Ck];
+ * proL / preL: [nlocal * B][Ck], local view i in rows i * B .. (train_3d.py:121's torch.cat).  Deterministic: two stages in fixed order,
+ * float64 arithmetic throughout (exact differences and products of the float32 inputs); three launches, no host synchronisation.  ws: pcrl_val_metrics_ws_bytes(B * S, B, nlocal). */
+size_t pcrl_val_metrics_ws_bytes(int64_t n, int B, int nlocal);
+int pcrl_val_metrics(const float* out1, const float* mask0, const float* mask1, const float* mask2, const float* gt,
+                     const float* pro1_0, const float* pre1_0, const float* pro2_0, const float* pre2_0, const float* proL_0, const float* preL_0,
+                     const float* pro1_1, const float* pre1_1, const float* pro2_1, const float* pre2_1, const float* proL_1, const float* preL_1,
+                     const float* pro1_2, const float* pre1_2, const float* pro2_2, const float* pre2_2, const float* proL_2, const float* preL_2,
+                     double* acc, void* ws, size_t ws_bytes, int B, int64_t S, int nlocal, int C0, int C1, int C2, float eps, pcrl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * OPTIONAL EXTRA, not part of the reference: NT-Xent (SimCLR) contrastive loss over z = [z1; z2], R = 2N

@@ -21,7 +21,8 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc",
 # allocator's default assignment order spills 9-17 registers there (fragment addresses, reloaded behind s_waitcnt vmcnt(0) in the middle of a stage), the
 # reverse order fits all of them (profiles/r05_b16_isa_mix.txt).
 # augment2d.hip restates Pillow's and torch's CPU float arithmetic bit for bit, luna_prep.hip scipy's and ITK's float64 arithmetic: no fused multiply-adds.
-FILE_FLAGS = {"augment2d.hip": ["-ffp-contract=off"], "luna_prep.hip": ["-ffp-contract=off"], "conv_brick16.hip": ["-mllvm", "-greedy-reverse-local-assignment"], "conv_brick16_bnr.hip": ["-mllvm", "-greedy-reverse-local-assignment"]}
+FILE_FLAGS = {"augment2d.hip": ["-ffp-contract=off"], "luna_prep.hip": ["-ffp-contract=off"], "conv_brick16.hip": ["-mllvm", "-greedy-reverse-local-assignment"], "conv_brick16_bnr.hip": ["-mllvm", "-greedy-reverse-local-assignment"],
+              "conv_brick16_inf.hip": ["-mllvm", "-greedy-reverse-local-assignment"]}
 
 
 def hipcc() -> str:

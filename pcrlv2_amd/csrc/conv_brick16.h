@@ -87,6 +87,10 @@ struct Brick16Params {
   // the stored gradient.  bn_y: [N][D][H][W][Nc] bf16, the layout of y; bn_scale / bn_shift / bn_mean / bn_rstd: Nc floats each (pcrl_bn_finalize's outputs).
   const bf16* bn_y;
   const float *bn_scale, *bn_shift, *bn_mean, *bn_rstd;
+  // INF instantiations only (inference forward, conv_brick16_inf.hip): the epilogue stores a = max(bn_scale[co] * (acc + bias[co]) + bn_shift[co], act_lo)
+  // -- eval-mode BatchNorm (ops.bn_eval_coef's scale / shift) and the activation (act_lo = 0: ReLU, -inf: none) from the float32 accumulators; no
+  // pre-normalisation tensor, no statistics rows.
+  float act_lo;
 };
 
 __device__ __forceinline__ int key_w(int hw) { return ((0xFC30 >> hw) & 1) << 1; }   // hw in [0, 18)
@@ -119,8 +123,9 @@ __device__ __forceinline__ void lds_dma16_masked(uint64_t base, uint32_t voff, u
 // volume) -- for volumes whose H, not W, is a multiple of 16 (the 16 x 16 x 8 level).  A convolution commutes with a permutation of the axes
 // applied to volume, taps and phases alike: only the voxel index (VOX / FVOX), the tap number of a weight row (WTAP), the phase / parity bit of
 // an axis (BITH / BITW) and the border class (CLS) know the difference; rows still go through LDS one 64-byte slice per voxel.
-template <int BN, int MODE = 0, int PERM = 0, int NW = 4, bool BNR = false>
+template <int BN, int MODE = 0, int PERM = 0, int NW = 4, bool BNR = false, bool INF = false>
 __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) brick16_conv_kernel(const Brick16Params p) {
+  static_assert(!INF || (MODE == 0 && NW == 4 && !BNR), "the inference epilogue exists for the plain 4-plane forward only");
   static_assert(!BNR || ((MODE == 0 || MODE == 3) && NW == 4), "the BatchNorm-reduce epilogue exists for the plain 4-plane data gradient only (3D, and the 2D path's 3x3 form)");
   using G = B16Geom<NW>;
   constexpr int ROWS = G::ROWS, NDMA = G::NDMA, HALO_BYTES = G::HALO_BYTES, HD = G::HD;
@@ -492,6 +497,10 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) brick16_conv_kernel(
     s2[j] = 0.f;
     bv[j] = (!UPCF && !BNR && p.bias) ? p.bias[n0 + j * 16 + lr] : 0.f;   // BNR: a data gradient, no bias
     bvE[j] = 0.f;
+    if (INF) {
+      bsc[j] = p.bn_scale[n0 + j * 16 + lr];
+      bsh[j] = p.bn_shift[n0 + j * 16 + lr];
+    }
   }
   const int uch0 = UPCF ? n0 - uph * p.upc : 0;                       // first channel of this tile inside its phase
   const int ypitch = UPCF ? p.upc : p.Nc;
@@ -569,12 +578,13 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) brick16_conv_kernel(
       for (int j = 0; j < FN; ++j) {
         float bias = bv[j];
         if (UPCF && (r == 0 || r == 3)) bias = (elane && r == (pwb ? 3 : 0)) ? bvE[j] : bv[j];
-        const float val = acc[fm][j][r] + bias;
+        float val = acc[fm][j][r] + bias;
+        if (INF) val = fmaxf(fmaf(bsc[j], val, bsh[j]), p.act_lo);
         const bf16 vb = (bf16)val;
         *reinterpret_cast<bf16*>(yrow + yl + j * 32) = vb;
         if (BNR) {
           acc[fm][j][r] = (float)vb;   // the value as stored: what the separate reduce pass would read back
-        } else {
+        } else if (!INF) {
           s1[j] += val;
           s2[j] += val * val;
         }
@@ -661,19 +671,19 @@ inline int brick16_perm(int D, int H, int W) {
 
 
 // p.D / p.H / p.W arrive as the volume's extents; perm == 2: handed to the PERM instantiation as the extents along the brick axes (D, W, H)
-template <int BN, int MODE, int NW = 4, bool BNR = false>
+template <int BN, int MODE, int NW = 4, bool BNR = false, bool INF = false>
 inline int launch16(Brick16Params p, dim3 grid, hipStream_t stream, const char* what) {
   constexpr size_t lds = B16Geom<NW>::HALO_BYTES + 3 * BN * 64 + (NW == 4 ? 0 : 1024);   // NW = 8: + the halo plan's mask words
   static std::once_flag attr_once;
   std::call_once(attr_once, [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(brick16_conv_kernel<BN, MODE, 0, NW, BNR>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(brick16_conv_kernel<BN, MODE, 1, NW, BNR>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(brick16_conv_kernel<BN, MODE, 0, NW, BNR, INF>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(brick16_conv_kernel<BN, MODE, 1, NW, BNR, INF>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   });
   if (brick16_perm(p.D, p.H, p.W) == 2) {
     std::swap(p.H, p.W);
-    hipLaunchKernelGGL((brick16_conv_kernel<BN, MODE, 1, NW, BNR>), grid, dim3(NW * 64), lds, stream, p);
+    hipLaunchKernelGGL((brick16_conv_kernel<BN, MODE, 1, NW, BNR, INF>), grid, dim3(NW * 64), lds, stream, p);
   } else {
-    hipLaunchKernelGGL((brick16_conv_kernel<BN, MODE, 0, NW, BNR>), grid, dim3(NW * 64), lds, stream, p);
+    hipLaunchKernelGGL((brick16_conv_kernel<BN, MODE, 0, NW, BNR, INF>), grid, dim3(NW * 64), lds, stream, p);
   }
   return pcrl_check_launch(what);
 }

@@ -19,9 +19,16 @@ __device__ __forceinline__ bool tap_ok(int d, int h, int w, int kd, int kh, int 
 // First layer forward: y[m][c] = b[c] + sum_t x[m+delta_t] * w[c][t].  128 voxels per block (one BN-statistics
 // partial row, same granularity as the MFMA conv), 16 channels per thread, blockDim = 8*Co.
 // ------------------------------------------------------------------------------------------------
-template <typename T>
+// AFF instantiations (inference forward, pcrl_conv3d_k3_c1_fwd_affine): the stored value is max(scale[c] * (sum + bias[c]) + shift[c], act_lo) -- eval-mode
+// BatchNorm and the activation (act_lo = 0: ReLU, -inf: none) from the float32 sums; `stats` is null.
+struct C1Affine {
+  const float *scale, *shift;
+  float act_lo;
+};
+
+template <typename T, bool AFF = false>
 __global__ void c1_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w_ref, const float* __restrict__ bias,
-                              T* __restrict__ y, float* __restrict__ stats, Dims g, int64_t M, int Co) {
+                              T* __restrict__ y, float* __restrict__ stats, Dims g, int64_t M, int Co, C1Affine aff) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* wl = sm;             // [27][Co]
   float* red = sm + 27 * Co;  // [128][Co + 1]
@@ -49,6 +56,10 @@ __global__ void c1_fwd_kernel(const float* __restrict__ x, const float* __restri
 #pragma unroll
         for (int j = 0; j < 16; ++j) acc[j] += xv * wr[j];
       }
+    }
+    if (AFF) {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) acc[j] = fmaxf(fmaf(aff.scale[cg * 16 + j], acc[j], aff.shift[cg * 16 + j]), aff.act_lo);
     }
     T* yo = y + m * Co + cg * 16;
     constexpr int VEC = 16 / (int)sizeof(T);
@@ -101,10 +112,10 @@ __global__ void c1_fwd_kernel(const float* __restrict__ x, const float* __restri
 // Round 4: a block WALKS bricks (blockIdx.x, + gridDim.x, ...): the next brick's halo is requested before the current one is multiplied and stored
 // and lands under its MFMAs and stores (two LDS halo buffers), the weight fragments and tap offsets are built once per block -- the per-brick chain
 // stage -> im2col -> MFMA -> store becomes a pipeline.  Same arithmetic per brick, same statistics rows (one per brick): bit-identical.
-template <int CO>
+template <int CO, bool AFF = false>
 __global__ void __launch_bounds__(256, CO <= 32 ? 4 : 2) c1_brick_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w_ref,
                                                            const float* __restrict__ bias, bf16* __restrict__ y,
-                                                           float* __restrict__ stats, Dims g, int nbricks) {
+                                                           float* __restrict__ stats, Dims g, int nbricks, C1Affine aff) {
   constexpr int FN = CO / 16;
   __shared__ float sh[2][600];
   __shared__ float red[4 * CO * 2];
@@ -166,6 +177,14 @@ __global__ void __launch_bounds__(256, CO <= 32 ? 4 : 2) c1_brick_fwd_kernel(con
   float bv[FN];
 #pragma unroll
   for (int j = 0; j < FN; ++j) bv[j] = bias ? bias[j * 16 + lr] : 0.f;
+  float asc[FN], ash[FN];
+  if (AFF) {
+#pragma unroll
+    for (int j = 0; j < FN; ++j) {
+      asc[j] = aff.scale[j * 16 + lr];
+      ash[j] = aff.shift[j * 16 + lr];
+    }
+  }
   int b = blockIdx.x, cur = 0;
   if (b < nbricks) {
     C1_LOAD(b);
@@ -211,13 +230,16 @@ __global__ void __launch_bounds__(256, CO <= 32 ? 4 : 2) c1_brick_fwd_kernel(con
         char* const yrow = ybase + ((int64_t)(2 * f) * g.W + r) * (CO * 2);   // scalar
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
-          const float val = acc[f][j][r] + bv[j];
+          float val = acc[f][j][r] + bv[j];
+          if (AFF) val = fmaxf(fmaf(asc[j], val, ash[j]), aff.act_lo);
           *reinterpret_cast<bf16*>(yrow + yl + j * 32) = (bf16)val;
-          s1[j] += val;
-          s2[j] += val * val;
+          if (!AFF) {
+            s1[j] += val;
+            s2[j] += val * val;
+          }
         }
       }
-    if (stats) {
+    if (!AFF && stats) {
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
         float a = s1[j], c2 = s2[j];
@@ -457,33 +479,49 @@ extern "C" int64_t pcrl_conv3d_k3_c1_stats_rows(int N, int D, int H, int W, int 
   return ((int64_t)N * D * H * W + 127) / 128;
 }
 
-extern "C" int pcrl_conv3d_k3_c1_fwd(const float* x, const float* w_ref, const float* bias, void* y, float* stats_partial,
-                                     int N, int D, int H, int W, int Co, int dtype, pcrl_stream_t stream) {
-  PCRL_REQUIRE(x && w_ref && y, "conv3d_k3_c1_fwd: null pointer");
-  PCRL_REQUIRE(Co == 16 || Co == 32 || Co == 64, "conv3d_k3_c1_fwd: Co must be 16, 32 or 64 (got %d)", Co);
+template <bool AFF>
+static int c1_fwd_launch(const char* what, const float* x, const float* w_ref, const float* bias, void* y, float* stats_partial, C1Affine aff,
+                         int N, int D, int H, int W, int Co, int dtype, pcrl_stream_t stream) {
+  PCRL_REQUIRE(x && w_ref && y, "%s: null pointer", what);
+  PCRL_REQUIRE(Co == 16 || Co == 32 || Co == 64, "%s: Co must be 16, 32 or 64 (got %d)", what, Co);
+  PCRL_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "%s: bad dims %d %d %d %d", what, N, D, H, W);
   const Dims g{N, D, H, W};
   const int64_t M = (int64_t)N * D * H * W;
   if (c1_brick_ok(D, H, W, dtype)) {
     const int64_t nb64 = pcrl_conv3d_k3_c1_stats_rows(N, D, H, W, Co, dtype);
-    PCRL_REQUIRE(nb64 < ((int64_t)1 << 31), "conv3d_k3_c1_fwd: too many bricks");
+    PCRL_REQUIRE(nb64 < ((int64_t)1 << 31), "%s: too many bricks", what);
     const int nbr = (int)nb64;
     // persistent blocks: four per CU for the narrow forms (128 registers: the prefetch does not fit the 80 of six blocks per CU), two otherwise
     const int cap = 256 * (Co <= 32 ? 4 : 2);
     const unsigned bricks = (unsigned)(nbr < cap ? nbr : cap);
-    if (Co == 16) hipLaunchKernelGGL(c1_brick_fwd_kernel<16>, dim3(bricks), dim3(256), 0, as_stream(stream), x, w_ref, bias, (bf16*)y, stats_partial, g, nbr);
-    else if (Co == 32) hipLaunchKernelGGL(c1_brick_fwd_kernel<32>, dim3(bricks), dim3(256), 0, as_stream(stream), x, w_ref, bias, (bf16*)y, stats_partial, g, nbr);
-    else hipLaunchKernelGGL(c1_brick_fwd_kernel<64>, dim3(bricks), dim3(256), 0, as_stream(stream), x, w_ref, bias, (bf16*)y, stats_partial, g, nbr);
+    if (Co == 16) hipLaunchKernelGGL((c1_brick_fwd_kernel<16, AFF>), dim3(bricks), dim3(256), 0, as_stream(stream), x, w_ref, bias, (bf16*)y, stats_partial, g, nbr, aff);
+    else if (Co == 32) hipLaunchKernelGGL((c1_brick_fwd_kernel<32, AFF>), dim3(bricks), dim3(256), 0, as_stream(stream), x, w_ref, bias, (bf16*)y, stats_partial, g, nbr, aff);
+    else hipLaunchKernelGGL((c1_brick_fwd_kernel<64, AFF>), dim3(bricks), dim3(256), 0, as_stream(stream), x, w_ref, bias, (bf16*)y, stats_partial, g, nbr, aff);
     return pcrl_check_launch("c1_brick_fwd");
   }
   const unsigned blocks = (unsigned)((M + 127) / 128);
   const size_t lds = (size_t)(27 * Co + 128 * (Co + 1)) * sizeof(float);
   if (dtype == PCRL_BF16)
-    hipLaunchKernelGGL(c1_fwd_kernel<bf16>, dim3(blocks), dim3(8 * Co), lds, as_stream(stream), x, w_ref, bias, (bf16*)y, stats_partial, g, M, Co);
+    hipLaunchKernelGGL((c1_fwd_kernel<bf16, AFF>), dim3(blocks), dim3(8 * Co), lds, as_stream(stream), x, w_ref, bias, (bf16*)y, stats_partial, g, M, Co, aff);
   else if (dtype == PCRL_F32)
-    hipLaunchKernelGGL(c1_fwd_kernel<float>, dim3(blocks), dim3(8 * Co), lds, as_stream(stream), x, w_ref, bias, (float*)y, stats_partial, g, M, Co);
+    hipLaunchKernelGGL((c1_fwd_kernel<float, AFF>), dim3(blocks), dim3(8 * Co), lds, as_stream(stream), x, w_ref, bias, (float*)y, stats_partial, g, M, Co, aff);
   else
-    return pcrl_fail(PCRL_EINVAL, "conv3d_k3_c1_fwd: bad dtype %d", dtype);
+    return pcrl_fail(PCRL_EINVAL, "%s: bad dtype %d", what, dtype);
   return pcrl_check_launch("c1_fwd");
+}
+
+extern "C" int pcrl_conv3d_k3_c1_fwd(const float* x, const float* w_ref, const float* bias, void* y, float* stats_partial,
+                                     int N, int D, int H, int W, int Co, int dtype, pcrl_stream_t stream) {
+  return c1_fwd_launch<false>("conv3d_k3_c1_fwd", x, w_ref, bias, y, stats_partial, C1Affine{nullptr, nullptr, 0.f}, N, D, H, W, Co, dtype, stream);
+}
+
+// Inference forward of the first layer: convolution + eval-mode BatchNorm + activation (ReLU or none) in one pass, every shape and dtype of pcrl_conv3d_k3_c1_fwd
+extern "C" int pcrl_conv3d_k3_c1_fwd_affine(const float* x, const float* w_ref, const float* bias, const float* scale, const float* shift, void* a,
+                                            int N, int D, int H, int W, int Co, int act, int dtype, pcrl_stream_t stream) {
+  PCRL_REQUIRE(scale && shift, "conv3d_k3_c1_fwd_affine: null pointer");
+  PCRL_REQUIRE(act == PCRL_ACT_RELU || act == PCRL_ACT_NONE, "conv3d_k3_c1_fwd_affine: activation %d has no fused form (ReLU or none)", act);
+  const C1Affine aff{scale, shift, act == PCRL_ACT_RELU ? 0.f : -__builtin_inff()};
+  return c1_fwd_launch<true>("conv3d_k3_c1_fwd_affine", x, w_ref, bias, a, nullptr, aff, N, D, H, W, Co, dtype, stream);
 }
 
 static int to1_check(const char* what, int C, int taps, int dtype) {

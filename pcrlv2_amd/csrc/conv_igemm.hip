@@ -59,14 +59,19 @@ struct IgemmParams {
   // tile uses: 8-12 of 27 on a 2^3 grid, 15.6 on average on 4^3 (the local views' deepest levels).  Skipped taps contributed
   // exact zeros, so every output value is the one the full loop produces (split-K aside: the splits cut the shorter loop).
   int vmajor;
+  // AFF instantiations only (GEOM_CONV3, inference forward -- pcrl_conv3d_k3_fwd_affine): the one-pass epilogue stores
+  // max(aff_scale[co] * (acc + bias[co]) + aff_shift[co], act_lo) -- eval-mode BatchNorm and the activation (act_lo = 0: ReLU, -inf: none) -- and no statistics.
+  const float *aff_scale, *aff_shift;
+  float act_lo;
 };
 
 
 // PLANES: epilogue variant for the 1-output-channel convolutions (conv_c1.hip): the GEMM columns are the 27 taps of a
 // pointwise product z[t][m] = sum_c x[m][c] w[c][t]; the tile is written as float32, PLANE-major (z[col * M + m]), so the
 // shifted-sum pass that follows reads every plane contiguously.  No bias, no statistics.
-template <typename T, int BN, int GEOM, bool PLANES = false>
+template <typename T, int BN, int GEOM, bool PLANES = false, bool AFF = false>
 __global__ void __launch_bounds__(256, PCRL_OCC2) igemm_kernel(const IgemmParams p) {
+  static_assert(!AFF || (GEOM == GEOM_CONV3 && !PLANES), "the inference epilogue exists for the plain 3x3x3 forward only");
   constexpr int BM = PCRL_CONV_BM;
   using TL = Tile<T>;
   using MM = Mma<T>;
@@ -362,12 +367,16 @@ __global__ void __launch_bounds__(256, PCRL_OCC2) igemm_kernel(const IgemmParams
   }
   // ---- epilogue: bias, store, BN statistics ----
   T* __restrict__ Y = reinterpret_cast<T*>(p.y);
-  float s1[FN], s2[FN], bv[FN];
+  float s1[FN], s2[FN], bv[FN], asc[FN], ash[FN];
 #pragma unroll
   for (int j = 0; j < FN; ++j) {
     s1[j] = 0.f;
     s2[j] = 0.f;
     bv[j] = (p.bias && GEOM != GEOM_UPC_FWD) ? p.bias[n0 + wn * (BN / 2) + j * 16 + lr] : 0.f;
+    if (AFF) {
+      asc[j] = p.aff_scale[n0 + wn * (BN / 2) + j * 16 + lr];
+      ash[j] = p.aff_shift[n0 + wn * (BN / 2) + j * 16 + lr];
+    }
   }
 #pragma unroll
   for (int i = 0; i < FM; ++i) {
@@ -396,7 +405,8 @@ __global__ void __launch_bounds__(256, PCRL_OCC2) igemm_kernel(const IgemmParams
         }
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
-          const float v = acc[i][j][r] + bv[j];
+          float v = acc[i][j][r] + bv[j];
+          if (AFF) v = fmaxf(fmaf(asc[j], v, ash[j]), p.act_lo);
           Y[orow * p.Nc + n0 + wn * (BN / 2) + j * 16 + lr] = from_f<T>(v);
           s1[j] += v;
           s2[j] += v * v;
@@ -432,14 +442,21 @@ __global__ void __launch_bounds__(256, PCRL_OCC2) igemm_kernel(const IgemmParams
   }
 }
 
-template <typename T, int BN, int GEOM>
+template <typename T, int BN, int GEOM, bool AFF = false>
 int launch_igemm(const IgemmParams& p, int zdim, hipStream_t stream) {
   using TL = Tile<T>;
   const size_t lds = 2 * (size_t)(PCRL_CONV_BM + BN) * TL::ROWB;
   dim3 grid((unsigned)((p.M + PCRL_CONV_BM - 1) / PCRL_CONV_BM), (unsigned)(p.Nc / BN), (unsigned)zdim);
   if (GEOM == GEOM_UPC_FWD || GEOM == GEOM_UPC_DGRAD) grid = dim3((unsigned)(p.nt * p.zdim), (unsigned)(p.Nc / BN), (unsigned)(GEOM == GEOM_UPC_DGRAD ? zdim : 1));
-  hipLaunchKernelGGL((igemm_kernel<T, BN, GEOM>), grid, dim3(256), lds, stream, p);
+  hipLaunchKernelGGL((igemm_kernel<T, BN, GEOM, false, AFF>), grid, dim3(256), lds, stream, p);
   return pcrl_check_launch("igemm");
+}
+
+// inference forward (AFF): the 3x3x3 convolution with the eval-mode normalisation and the activation in the epilogue, one pass (no split-K)
+template <typename T> int dispatch_affine_bn(const IgemmParams& p, hipStream_t stream) {
+  if (p.Nc % 128 == 0) return launch_igemm<T, 128, GEOM_CONV3, true>(p, 1, stream);
+  if (p.Nc % 64 == 0) return launch_igemm<T, 64, GEOM_CONV3, true>(p, 1, stream);
+  return launch_igemm<T, 32, GEOM_CONV3, true>(p, 1, stream);
 }
 
 template <typename T, int GEOM> int dispatch_bn(const IgemmParams& p, int zdim, hipStream_t stream) {
@@ -644,6 +661,48 @@ extern "C" int64_t pcrl_conv3d_k3_fwd_ws_bytes(int N, int D, int H, int W, int C
 extern "C" int pcrl_conv3d_k3_fwd_ws(const void* x, const void* wp, const float* bias, void* y, float* stats_partial, void* ws,
                                      int64_t ws_bytes, int N, int D, int H, int W, int Ci, int Co, int dtype, pcrl_stream_t stream) {
   return conv3d_k3_fwd_impl(x, wp, bias, y, stats_partial, ws, ws_bytes, N, D, H, W, Ci, Co, dtype, stream);
+}
+
+// ---- inference forward: convolution + eval-mode BatchNorm + activation in one pass (wide-brick: conv_brick16_inf.hip; gather: AFF above) ----
+int pcrl_brick16_conv_affine_launch(const void* x, const void* wp, const float* bias, const float* scale, const float* shift, float act_lo, void* a,
+                                    int N, int D, int H, int W, int Ci, int Co, hipStream_t stream);
+// The route ops.luconv_infer takes -- 2: wide-brick kernel, 1: gather kernel in one pass, 0: conv + apply as two passes, because the unfused convolution
+// of the shape runs on a kernel family without a fused form (4x8x8 bricks, split-K, voxel-major rows).  pcrl_conv3d_k3_fwd_affine itself computes every
+// shape: the wide-brick kernel where eligible, else the gather kernel in one pass.
+static int conv3d_k3_affine_route(int N, int D, int H, int W, int Ci, int Co, int dtype) {
+  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || Ci % 32 != 0 || Co % 32 != 0) return 0;
+  if (dtype != PCRL_BF16 && dtype != PCRL_F32) return 0;
+  if (g_conv_impl == 0 && pcrl_brick16_conv_eligible(N, D, H, W, Ci, Co, dtype)) return 2;
+  if (g_conv_impl == 0 && pcrl_brick_conv_eligible(N, D, H, W, Ci, Co, dtype)) return 0;
+  const int vtaps = conv3_vmajor_taps(N, D, H, W);
+  if (vtaps) return 0;
+  if (g_conv_impl != 2 && splitk_plan((int64_t)N * D * H * W, Ci, Co, 27).splits > 1) return 0;
+  return 1;
+}
+extern "C" int64_t pcrl_conv3d_k3_fwd_affine_fused(int N, int D, int H, int W, int Ci, int Co, int dtype) {
+  return conv3d_k3_affine_route(N, D, H, W, Ci, Co, dtype) != 0;
+}
+extern "C" int64_t pcrl_conv3d_k3_fwd_affine_ws_bytes(int N, int D, int H, int W, int Ci, int Co, int dtype) {
+  (void)N; (void)D; (void)H; (void)W; (void)Ci; (void)Co; (void)dtype;
+  return 0;   // every fused form is one pass
+}
+extern "C" int pcrl_conv3d_k3_fwd_affine(const void* x, const void* wp, const float* bias, const float* scale, const float* shift, void* a, void* ws,
+                                         int64_t ws_bytes, int N, int D, int H, int W, int Ci, int Co, int act, int dtype, pcrl_stream_t stream) {
+  (void)ws; (void)ws_bytes;
+  if (int e = check_dims("conv3d_k3_fwd_affine", N, D, H, W, Ci, Co)) return e;
+  PCRL_REQUIRE(x && wp && scale && shift && a, "conv3d_k3_fwd_affine: null pointer");
+  PCRL_REQUIRE(act == PCRL_ACT_RELU || act == PCRL_ACT_NONE, "conv3d_k3_fwd_affine: activation %d has no fused form (ReLU or none)", act);
+  PCRL_REQUIRE(dtype == PCRL_BF16 || dtype == PCRL_F32, "conv3d_k3_fwd_affine: bad dtype %d", dtype);
+  const int route = conv3d_k3_affine_route(N, D, H, W, Ci, Co, dtype);
+  const float act_lo = act == PCRL_ACT_RELU ? 0.f : -__builtin_inff();
+  if (route == 2) return pcrl_brick16_conv_affine_launch(x, wp, bias, scale, shift, act_lo, a, N, D, H, W, Ci, Co, as_stream(stream));
+  IgemmParams p{x, wp, bias, a, nullptr, Dims{N, D, H, W}, (int64_t)N * D * H * W, Ci, Co, 27, nullptr, 0};
+  p.vmajor = 0;
+  p.aff_scale = scale;
+  p.aff_shift = shift;
+  p.act_lo = act_lo;
+  if (dtype == PCRL_BF16) return dispatch_affine_bn<bf16>(p, as_stream(stream));
+  return dispatch_affine_bn<float>(p, as_stream(stream));
 }
 
 // ---- data gradient + first pass of the BatchNorm backward of the layer below (conv_brick16_bnr.hip) ----

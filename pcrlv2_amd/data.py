@@ -373,6 +373,7 @@ class AugmentedLoader:
                                                       persistent_workers=workers > 0, prefetch_factor=4 if workers > 0 else None,
                                                       worker_init_fn=worker_affinity_init if workers > 0 else None)
         self.augment = kind.augment(device, seed) if kind is not None else GpuLunaAugment(device, seed)
+        self.seed = seed
         self._stream = None
         self._ring, self._ring_pos = None, 0
         self._events = []
@@ -380,6 +381,15 @@ class AugmentedLoader:
 
     def __len__(self):
         return len(self.loader)
+
+    def reset_rng(self):
+        """The augmentation's device generator and its host companion back to the loader's seed (train_3d.validate: every validation pass
+        draws the same augmentations)."""
+        gen, host = getattr(self.augment, "gen", None), getattr(self.augment, "host_rng", None)
+        if gen is not None:
+            gen.manual_seed(self.seed)
+        if host is not None:
+            host.seed(self.seed)
 
     @staticmethod
     def _tensors(batch):
@@ -495,6 +505,31 @@ class AugmentedLoader:
                 tm[k] = 0
 
 
+def eval_shard(files, rank, world):
+    """Rank `rank`'s part of the validation files: disjoint contiguous runs that cover the list (sizes differ by at most one; validation ends
+    in ONE all-reduce of sums, so the ranks need not run the same number of batches)."""
+    n = len(files)
+    return list(files[rank * n // world:(rank + 1) * n // world])
+
+
+class _LazyLoaders(dict):
+    """{'train': ..., 'eval': ...} (data.py:63-99) whose 'eval' loader -- and its worker processes and shared batch slots -- is built when
+    somebody first asks for it: the reference builds it and never reads it, and a run without --val_every does not either."""
+
+    def __init__(self, train, make_eval):
+        super().__init__(train=train, eval=None)
+        self._make_eval = make_eval
+
+    def __getitem__(self, key):
+        if key == "eval" and self._make_eval is not None:
+            make, self._make_eval = self._make_eval, None
+            super().__setitem__("eval", make())
+        return super().__getitem__(key)
+
+    def get(self, key, default=None):
+        return self[key] if key in self else default
+
+
 def luna_pretask_loaders(args, device=None):
     """`DataGenerator(args).pcrlv2_luna_pretask()` (data.py:63-99): {'train': ..., 'eval': ...}."""
     device = device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu")
@@ -508,5 +543,14 @@ def luna_pretask_loaders(args, device=None):
     # reference's loader (data.py:90-93: drop_last=False).
     if world > 1:
         x_train = x_train[:len(x_train) - len(x_train) % world]
-    return {"train": AugmentedLoader(x_train[rank::world], args.b, args.workers, device, True, seed + rank, drop_last=world > 1),
-            "eval": AugmentedLoader(x_valid, args.b, args.workers, device, False, seed)}
+    x_valid = eval_shard(x_valid, rank, world)
+
+    def make_eval():
+        ev = AugmentedLoader(x_valid, args.b, args.workers, device, False, seed)
+        try:
+            ev.sharded = True       # built for this rank: train_3d.validate takes it whole
+        except AttributeError:
+            pass
+        return ev
+
+    return _LazyLoaders(AugmentedLoader(x_train[rank::world], args.b, args.workers, device, True, seed + rank, drop_last=world > 1), make_eval)

@@ -43,6 +43,9 @@ _FLAGS = (
     ("resume", "", str, "checkpoint to continue from (model, momentum buffers, epoch)"),
     ("encoder_weights", "", str, "only with --d 2: local ResNet-18 state_dict (torchvision key names) for the encoder; empty = random init "
                                  "(the reference's smp.Unet('resnet18') downloads ImageNet weights, which an offline engine cannot)"),
+    ("val_every", 0, int, "only with --d 3: held-out validation (folds 7-9; a second synthetic stream with --data synthetic) after every N-th epoch; "
+                          "0 = never, like the reference"),
+    ("save_best", False, None, "with --val_every: write <model>_<n>_<phase>_<ratio>_best.pt whenever the validation total improves"),
     ("size2d", 224, int, "only with --d 2 --data synthetic: side of the global views (locals are 96x96)"),
 )
 
@@ -65,10 +68,14 @@ class SyntheticLunaLoader:
     def __init__(self, b, steps, seed=0, device=None):
         import torch
         self.device = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
-        self.b, self.steps, self.g = b, steps, torch.Generator(device=self.device).manual_seed(seed)
+        self.b, self.steps, self.seed, self.g = b, steps, seed, torch.Generator(device=self.device).manual_seed(seed)
 
     def __len__(self):
         return self.steps
+
+    def reset_rng(self):
+        """Back to the first batch of the stream (train_3d.validate: every validation pass sees the same data)."""
+        self.g.manual_seed(self.seed)
 
     def __iter__(self):
         import torch
@@ -111,7 +118,10 @@ def get_dataloader(args):
     if args.data == 'synthetic' and args.d == 2:
         return {'train': SyntheticChestLoader(args.b, args.steps_per_epoch, args.size2d, args.seed + int(os.environ.get("RANK", "0"))), 'eval': None}
     if args.data == 'synthetic':
-        return {'train': SyntheticLunaLoader(args.b, args.steps_per_epoch, args.seed + int(os.environ.get("RANK", "0"))), 'eval': None}
+        rank = int(os.environ.get("RANK", "0"))
+        ev = SyntheticLunaLoader(args.b, args.steps_per_epoch, args.seed + 7919 + rank)      # another stream than any rank's training data
+        ev.sharded = True                                                                  # one stream per rank: nothing to cut
+        return {'train': SyntheticLunaLoader(args.b, args.steps_per_epoch, args.seed + rank), 'eval': ev}
     if args.d == 2 and os.path.isdir(args.data):
         from .data_chest import chest_pretask_loaders     # images from disk, the torchvision chain on the GPU (data.py:14-61)
         return chest_pretask_loaders(args)

@@ -252,6 +252,20 @@ class PCRLv23d(nn.Module):
     def _forward_eval(self, x, local):
         """`model.eval()` forward (what a consumer of the checkpoint runs for validation, README.md:48-55): the same kernels with every
         BatchNorm on its RUNNING statistics, nothing updated, no autograd graph (inference only: fine-tuning runs in train mode)."""
+        return self._eval_stages(x, local, fused=False)
+
+    @torch.no_grad()
+    def infer(self, x, local=False, *, features_only=False):
+        """The eval-mode forward on the inference kernels (engine extension): the values of `model.eval()(x, local)` -- in bf16 up to the one
+        rounding of the pre-normalisation tensor that this path does not perform -- with every BatchNorm + ReLU LUConv as ONE launch
+        (ops.luconv_infer: normalisation and activation in the convolution's epilogue).  Whatever `self.training` says; no parameter, running
+        statistic, counter or attribute of the model is touched.  features_only: (None, features, []) -- the reconstruction, the deep-supervision
+        maps and their upsampling are skipped (the second view and the local views of train_3d.validate)."""
+        if not x.is_cuda:
+            raise RuntimeError("PCRLv23d (pcrlv2_amd) runs on the GPU only: input is on %s and there is no CPU fallback" % x.device)
+        return self._eval_stages(x, local, fused=True, features_only=features_only)
+
+    def _eval_stages(self, x, local, fused, features_only=False):
         dt = self.compute_dtype
 
         def lu(m, h):
@@ -259,7 +273,10 @@ class PCRLv23d(nn.Module):
             w = c.weight
             if m._ci_pad:
                 h, w = ops.pad_first_layer(h, w, m._ci_pad, dt)
-            return ops.luconv_forward(h, w, c.bias, n.weight, n.bias, None if gn else n.running_mean, None if gn else n.running_var,
+            rm, rv = (None, None) if gn else (n.running_mean, n.running_var)
+            if fused:
+                return ops.luconv_infer(h, w, c.bias, n.weight, n.bias, rm, rv, m._packed, m._act, dt, gn_groups=gn, prelu=Fn._slope(m), inorm=m._inorm)
+            return ops.luconv_forward(h, w, c.bias, n.weight, n.bias, rm, rv,
                                       m._packed, m._act, dt, training=False, gn_groups=gn, prelu=Fn._slope(m), inorm=m._inorm)[0]
 
         h = x.float().contiguous()
@@ -268,7 +285,8 @@ class PCRLv23d(nn.Module):
                 h = ops.maxpool_forward(ops.to_act(h, dt), dt)
             st = getattr(self, name)
             h = lu(st.ops[1], lu(st.ops[0], h))
-            setattr(self, attr, h)
+            if not fused:
+                setattr(self, attr, h)
         feats, masks = [], []
         for (name, _, _), factor in zip(_DECODER, _UPSAMPLE):
             up = getattr(self, name)
@@ -277,9 +295,11 @@ class PCRLv23d(nn.Module):
             pro = ops.bn1d_eval(ops.gap_forward(h, dt), up.bn.weight, up.bn.bias, up.bn.running_mean, up.bn.running_var, relu=False)
             hid = ops.bn1d_eval(ops.linear_forward(pro, ph[0].weight, ph[0].bias), ph[1].weight, ph[1].bias, ph[1].running_mean, ph[1].running_var, relu=True)
             feats.append([pro, ops.linear_forward(hid, ph[3].weight, ph[3].bias)])
-            if not local:
+            if not local and not features_only:
                 mask = lu(up.deep_supervision_head, h)
                 masks.append(mask if factor == 1 else ops.upsample_forward(mask, factor))
+        if features_only:
+            return None, feats, []
         return ops.conv1x1_to1_forward(ops.to_act(h, dt), self.out_tr.final_conv.weight, self.out_tr.final_conv.bias, dt), feats, masks
 
     def _train_stages(self, x, local, pass_idx, features_only=False, lazy_skips=False):

@@ -927,6 +927,75 @@ def luconv_forward(x, conv_w, conv_b, gamma, beta, running_mean, running_var, pa
     return a, sv
 
 
+INFER_FUSED = True      # module attribute (tools/val_forward_probe.py flips it): False = luconv_infer always runs conv + apply
+
+
+def infer_fused_route(N, D, H, W, Ci, Co, act, dtype, norm_is_bn=True) -> bool:
+    """Host only: does luconv_infer run this eval-mode LUConv as ONE kernel (convolution with normalisation + activation in its epilogue)?"""
+    if not (INFER_FUSED and norm_is_bn) or act not in (ACT_RELU, ACT_NONE) or Co == 1:
+        return False
+    if Ci == 1:
+        return Co in (16, 32, 64)
+    return bool(lib().call("pcrl_conv3d_k3_fwd_affine_fused", N, D, H, W, Ci, Co, dtype_code(dtype)))
+
+
+def luconv_infer(x, conv_w, conv_b, gamma, beta, running_mean, running_var, packed: PackedWeights, act: int, dtype, gn_groups=0, prelu=None,
+                 inorm=False):
+    """Eval-mode LUConv for inference (PCRLv23d.infer): conv -> BatchNorm on the running statistics -> activation, no autograd, nothing
+    updated.  BatchNorm + ReLU / no activation on the kernel families that have the epilogue (infer_fused_route): ONE launch -- the normalisation
+    and the activation are applied to the convolution's float32 accumulators, the pre-normalisation tensor is never written.  Everything
+    else (GroupNorm / InstanceNorm, PReLU / ELU / SiLU / sigmoid, the 1-channel heads, 4x8x8-brick and split-K shapes): luconv_forward(training=False),
+    i.e. conv + apply as two passes."""
+    Co, Ci = conv_w.shape[0], conv_w.shape[1]
+    bn = not gn_groups and not inorm and prelu is None
+    if Ci == 1:
+        N, _, D, H, W = x.shape
+    else:
+        N, D, H, W, _ = dims(x)
+    if not infer_fused_route(N, D, H, W, Ci, Co, act, dtype, bn):
+        return luconv_forward(x, conv_w, conv_b, gamma, beta, running_mean, running_var, packed, act, dtype, training=False, gn_groups=gn_groups,
+                              prelu=prelu, inorm=inorm)[0]
+    L, s, dev = lib(), stream_handle(), x.device
+    scale, shift = bn_eval_coef(gamma, beta, running_mean, running_var)
+    a = new_act(N, D, H, W, Co, dtype, dev)
+    if Ci == 1:
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.shape[1] != 1:
+            raise PcrlError("first-layer input must be a contiguous float32 [N,1,D,H,W] tensor")
+        L.call("pcrl_conv3d_k3_c1_fwd_affine", x, conv_w.detach(), conv_b.detach(), scale, shift, a, N, D, H, W, Co, act, dtype_code(dtype), s)
+        return a
+    if x.shape[1] != Ci:
+        raise PcrlError(f"LUConv: input has {x.shape[1]} channels, weight expects {Ci}")
+    if x.dtype != dtype:
+        raise PcrlError(f"LUConv: activation dtype {x.dtype} != compute dtype {dtype}")
+    wf, _ = packed.get(conv_w, dtype)
+    nb = L.call("pcrl_conv3d_k3_fwd_affine_ws_bytes", N, D, H, W, Ci, Co, dtype_code(dtype))
+    L.call("pcrl_conv3d_k3_fwd_affine", x, wf, conv_b.detach(), scale, shift, a, workspace(nb, dev) if nb else None, nb, N, D, H, W, Ci, Co, act,
+           dtype_code(dtype), s)
+    return a
+
+
+def val_metrics(out1, masks, gt, feats1, feats2, feats_loc, acc):
+    """One batch's validation metrics added to `acc` (float64 [11] on the device: ten batch-size-weighted sums + the sample count; pcrl_val_metrics).
+    out1, masks[k], gt: float32 [B,1,D,H,W]; feats*[k] = [projection, prediction] float32 [rows, C_k], feats_loc rows = nlocal * B."""
+    L, s = lib(), stream_handle()
+    B = out1.shape[0]
+    S = out1.numel() // B
+    nlocal = feats_loc[0][0].shape[0] // B
+    if len(masks) != 3 or len(feats1) != 3 or feats_loc[0][0].shape[0] != nlocal * B or nlocal < 1:
+        raise PcrlError("val_metrics: three scales and nlocal * B local rows expected")
+    f32 = lambda t: t.detach().float().contiguous()
+    maps = [f32(t) for t in (out1, *masks, gt)]
+    if any(t.numel() != B * S for t in maps):
+        raise PcrlError("val_metrics: out1, the three masks and gt must have the same number of elements")
+    fl = []
+    for k in range(3):
+        fl += [f32(feats1[k][0]), f32(feats1[k][1]), f32(feats2[k][0]), f32(feats2[k][1]), f32(feats_loc[k][0]), f32(feats_loc[k][1])]
+    C = [feats1[k][0].shape[1] for k in range(3)]
+    nb = L.call("pcrl_val_metrics_ws_bytes", B * S, B, nlocal)
+    L.call("pcrl_val_metrics", *maps, *fl, acc, workspace(nb, out1.device), nb, B, S, nlocal, C[0], C[1], C[2], 1e-8, s)
+    return acc
+
+
 def take_pre_partial(sv: LUConvSaved, da):
     """The first BatchNorm-backward pass of `sv`'s layer if the data gradient above it already took it for exactly this gradient tensor
     (luconv_backward's `bnred`), else None.  One-shot."""

@@ -243,6 +243,82 @@ def train_step(model, optimizer, batch, epoch, criterion, cosine, guard=True):
     return out
 
 
+VAL_KEYS = ("mse_out", "mse_mid0", "mse_mid1", "mse_mid2", "cos_global0", "cos_global1", "cos_global2", "cos_local0", "cos_local1", "cos_local2")
+
+
+def val_beta(epoch):
+    """The deep-supervision weight of train_3d.py:136 (240 hard-coded there, Q2)."""
+    return 0.5 * (1.0 + math.cos(math.pi * epoch / BETA_PERIOD))
+
+
+def val_total(m, epoch):
+    """The expectation of the training loss (train_3d.py:135-138) over its uniform scale draws, from the ten per-scale means."""
+    mean3 = lambda name: (m[name + "0"] + m[name + "1"] + m[name + "2"]) / 3.0
+    return m["mse_out"] + mean3("cos_global") + mean3("cos_local") + val_beta(epoch) * mean3("mse_mid")
+
+
+def _val_shard(loader, group):
+    """The batches this rank evaluates.  A loader that was built for this rank (luna_pretask_loaders: a contiguous shard of the validation
+    files per rank; anything with `sharded = True`) is taken whole; a loader with `shard(rank, world)` is asked; a plain sequence of batches
+    is cut into contiguous runs."""
+    world = dist.get_world_size(group) if group is not None or (dist.is_available() and dist.is_initialized()) else 1
+    if world <= 1 or getattr(loader, "sharded", False):
+        return loader
+    rank = dist.get_rank(group)
+    if hasattr(loader, "shard"):
+        return loader.shard(rank, world)
+    if isinstance(loader, (list, tuple)):
+        n = len(loader)
+        return loader[rank * n // world:(rank + 1) * n // world]
+    raise TypeError("validate: with a process group the loader must be sharded per rank (`sharded = True`), offer shard(rank, world), or be a sequence of batches")
+
+
+def validate(model, loader, epoch, group=None):
+    """One pass over held-out data (the reference builds `dataloader['eval']` over folds 7-9, data.py:63-99, and never reads it): the terms of
+    the training loss in eval mode at EVERY scale index -- so no random number is drawn and the total is the expectation of train_3d.py:135-138
+    over its draws, comparable to the training log.  Per batch: PCRLv23d.infer on view 1, on view 2 (features only) and on the concatenated local
+    views, then pcrl_val_metrics into a device accumulator; ONE host synchronisation and read-back at the end (after ONE all_reduce of the eleven
+    sums when there is a process group of more than one rank).  The loader's augmentation generator is reset to its seed first (`reset_rng()`):
+    every pass sees the same data, two passes on the same weights give bit-identical numbers.  `model.training` is not changed.
+    -> {'mse_out', 'mse_mid0..2', 'cos_global0..2', 'cos_local0..2', 'total', 'n'}; sample-weighted means (a ragged last batch counts by its size)."""
+    dev = next(model.parameters()).device
+    if hasattr(loader, "reset_rng"):
+        loader.reset_rng()
+    distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
+    acc = torch.zeros(len(VAL_KEYS) + 1, dtype=torch.float64, device=dev)
+    with torch.no_grad():
+        for batch in (_val_shard(loader, group) if distributed else loader):
+            view1, view2, target, _gt2, local_views = batch
+            view1, view2, target = _to_gpu(view1), _to_gpu(view2), _to_gpu(target)
+            out1, feats1, masks1 = model.infer(view1)
+            _, feats2, _ = model.infer(view2, features_only=True)
+            loc = _ops.concat_batch([_to_gpu(v) for v in local_views])
+            _, feats_loc, _ = model.infer(loc, local=True, features_only=True)
+            _ops.val_metrics(out1, masks1, target, feats1, feats2, feats_loc, acc)
+    if distributed:
+        dist.all_reduce(acc, group=group)
+    host = acc.cpu().tolist()          # the pass's one synchronisation
+    n = host[-1]
+    out = {k: (v / n if n else float("nan")) for k, v in zip(VAL_KEYS, host)}
+    out["total"] = val_total(out, epoch)
+    out["n"] = int(round(n))
+    return out
+
+
+def _best_checkpoint_name(args):
+    return os.path.join(args.output, "{}_{}_{}_{}_best.pt".format(args.model, args.n, args.phase, args.ratio))
+
+
+def save_if_best(args, model, optimizer, epoch, val, best):
+    """--save_best: the checkpoint layout of train_3d.py:71-82 plus 'val' (validate's dict), written whenever `total` improves strictly.
+    -> the best total so far."""
+    if best is not None and not val["total"] < best:
+        return best
+    torch.save({'opt': args, 'state_dict': model.state_dict(), 'optimizer': optimizer.state_dict(), 'epoch': epoch, 'val': dict(val)},
+               _best_checkpoint_name(args))
+    return val["total"]
+
+
 def _checkpoint_name(args, epoch):
     return os.path.join(args.output, "{}_{}_{}_{}_{}.pt".format(args.model, args.n, args.phase, args.ratio, epoch))
 
@@ -292,6 +368,7 @@ def _train_pcrlv2_3d(args, data_loader, distributed):
     if distributed:
         _ddp.DataParallel(model, optimizer)          # hooks itself into optimizer.step()
     criterion, cosine = MSELoss().cuda(), CosineSimilarityMean().cuda()
+    val_every, best_total = int(getattr(args, "val_every", 0) or 0), None
 
     for epoch in range(first_epoch, args.epochs + 1):          # inclusive upper bound, like the reference (Q1): lr reaches 0 in the last epoch
         adjust_learning_rate(epoch, args, optimizer)
@@ -305,6 +382,15 @@ def _train_pcrlv2_3d(args, data_loader, distributed):
                 print('==> Saving...')
                 torch.save({'opt': args, 'state_dict': model.state_dict(), 'optimizer': optimizer.state_dict(), 'epoch': epoch},
                            _checkpoint_name(args, epoch))
+        if val_every > 0 and (epoch + 1) % val_every == 0:      # --val_every N: held-out metrics after every N-th epoch (0: never -- the reference)
+            val = validate(model, data_loader['eval'], epoch)
+            if chatty:
+                mean3 = lambda name: (val[name + "0"] + val[name + "1"] + val[name + "2"]) / 3.0
+                print('Val: [{0}]\ttotal {1:.4f}\tmg {2:.4f}\tcos {3:.4f}\tlocal {4:.4f}\tmid {5:.4f}\t({6} samples)'.format(
+                    epoch, val["total"], val["mse_out"], mean3("cos_global"), mean3("cos_local"), mean3("mse_mid"), val["n"]))
+                sys.stdout.flush()
+                if getattr(args, "save_best", False):
+                    best_total = save_if_best(args, model, optimizer, epoch, val, best_total)
         if _cfg.EMPTY_CACHE_PER_EPOCH:           # the reference's per-epoch empty_cache (train_3d.py:83 / train_2d.py:108); the steady-state pools are kept (ops.empty_cache)
             torch.cuda.empty_cache() if _cfg.EMPTY_CACHE_RAW else _ops.empty_cache()
     return model
