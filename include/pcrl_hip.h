@@ -373,7 +373,8 @@ int64_t pcrl_conv2d_fwd_stats_only_ok(int N, int Hi, int Wi, int CiP, int Co, in
  * models/pcrlv2_model.py:114) INCLUDING the upsample's backward (aten::convolution_backward's input gradient + aten::upsample_nearest2d_backward):
  * dx[N][Hc][Wc][Ci] = 2 x 2 block sums of the fine-resolution gradient, which is never stored.  dy: [N][2Hc][2Wc][CoP]; wp_dgrad as for
  * pcrl_conv2d_dgrad.  Only where pcrl_conv2d_dgrad_up_ok() != 0 (both channel counts <= 32, bf16, fine extents multiples of 8 x 32). */
-/* which kernel the dispatcher runs for a geometry (no launch): 0 gather implicit GEMM, 1 LDS-halo brick kernel, 2 right-sized narrow kernel */
+/* which kernel the dispatcher runs for a geometry (no launch): 0 gather implicit GEMM, 1 LDS-halo brick kernel, 2 right-sized narrow kernel,
+ * 3 wide-brick kernel */
 int64_t pcrl_conv2d_fwd_kind(int N, int Hi, int Wi, int CiP, int Co, int KH, int KW, int stride, int pad, int up, int out_f32, int dtype);
 int64_t pcrl_conv2d_dgrad_kind(int N, int Hi, int Wi, int Ci, int Ho, int Wo, int CoP, int KH, int KW, int stride, int pad, int dtype);
 int64_t pcrl_conv2d_dgrad_up_ok(int N, int Hc, int Wc, int Ci, int CoP, int dtype);
@@ -584,15 +585,15 @@ int pcrl_prep_windows(const int16_t* vol, int X, int Y, int Z, const int64_t* re
 /* ---------------------------------------------------------------------------------------
  * Test hooks (NOT part of the drop-in surface; process-wide atomics, default 0 / tr 1 = the product path).  They select which
  * of the kernels behind one entry point runs, so that tests can check every kernel against the same reference and probes can
- * time them against each other inside one process (tools/conv_probe.py).
- *   conv  impl: 0 auto (LDS-halo brick kernel where eligible, co-located launch), 1 gather kernel, 2 gather kernel without
- *               split-K, 3 brick kernel on its plain 2-D grid, 4 the 4x8x8-brick kernel also where the 4x8x16-brick one is eligible,
- *               5 / 6 auto with the wide-brick kernel on 4 x 8 x 16 bricks only / on 8 x 8 x 16 bricks wherever they tile
- *   wgrad impl: 0 auto (brick kernel where eligible, XCD co-located launch), 1 gather kernel, 2 brick kernel on its plain 2-D grid,
- *               4 / 5 co-located launch with the old walk order / plain grid with the new walk order (experiments),
+ * time them against each other inside one process (tools/conv_probe.py).  The state they set and the code tables live in csrc/core.hip.
+ *   conv  impl: 0 auto (wide-brick kernel, else 4x8x8-brick kernel, where eligible; co-located launch), 1 gather kernel, 2 gather kernel
+ *               without split-K, 3 4x8x8-brick kernel on its plain 2-D grid, 4 the 4x8x8-brick kernel also where the 4x8x16-brick one is
+ *               eligible, 5 / 6 auto with the wide-brick kernel on 4 x 8 x 16 bricks only / on 8 x 8 x 16 bricks wherever they tile
+ *   wgrad impl: 0 auto (brick kernel where eligible, XCD co-located launch), 1 gather kernel, 2 brick kernel on its plain 2-D grid with the
+ *               old walk order, 4 / 5 co-located launch with the old walk order / plain grid with the new walk order (experiments),
  *               6 co-located launch with 64 x 64 tiles only (0 also uses 128 x 64, 64 x 128 and 64 x 32 tiles)
  *   wgrad tr  : bf16 fragment fetch of the gather weight-gradient kernel: 1 ds_read_b64_tr_b16, 0 scalar LDS reads
- *   conv2d impl: 0 auto (brick / narrow kernels where eligible), 1 gather kernel */
+ *   conv2d impl: 0 auto (wide-brick / brick / narrow kernels where eligible), 1 gather kernel, 2 auto without the wide-brick kernel */
 void pcrl_debug_set_conv_impl(int impl);
 void pcrl_debug_set_wgrad_impl(int impl);
 void pcrl_debug_set_wgrad_tr(int on);

@@ -79,18 +79,9 @@ class _Lib:
         self.profiler = None
         self.counter = None
         self._kinds = {}
-        self.debug_set_wgrad_tr = self.cdll.pcrl_debug_set_wgrad_tr
-        self.debug_set_wgrad_tr.argtypes = [ctypes.c_int]
-        self.debug_set_wgrad_tr.restype = None
-        self.debug_set_wgrad_impl = self.cdll.pcrl_debug_set_wgrad_impl
-        self.debug_set_wgrad_impl.argtypes = [ctypes.c_int]
-        self.debug_set_wgrad_impl.restype = None
-        self.debug_set_conv_impl = self.cdll.pcrl_debug_set_conv_impl
-        self.debug_set_conv_impl.argtypes = [ctypes.c_int]
-        self.debug_set_conv_impl.restype = None
-        self.debug_set_conv2d_impl = self.cdll.pcrl_debug_set_conv2d_impl
-        self.debug_set_conv2d_impl.argtypes = [ctypes.c_int]
-        self.debug_set_conv2d_impl.restype = None
+        for name in self.protos:     # the test hooks (pcrl_debug_set_conv_impl, ...) as plain attributes: lib().debug_set_conv_impl(1)
+            if name.startswith("pcrl_debug_set_"):
+                setattr(self, name[len("pcrl_"):], self.fn[name][0])
 
     def version(self) -> str:
         return self.fn["pcrl_version"][0]().decode()

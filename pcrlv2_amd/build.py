@@ -16,7 +16,9 @@ LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libpcrl_hip.so")
 OBJDIR = os.path.join(os.path.dirname(PKG), "build", "obj")
 ARCH = "gfx950"
-FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
+FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
+         # a function that crosses a translation unit is declared in a header (csrc/internal.h, include/pcrl_hip.h); everything else has internal linkage
+         "-Wmissing-prototypes", "-Werror=missing-prototypes"]
 # Per-file code generation flags.  conv_brick16.hip: the plain wide-brick instantiations sit at the 256-register budget of two waves per SIMD; the greedy
 # allocator's default assignment order spills 9-17 registers there (fragment addresses, reloaded behind s_waitcnt vmcnt(0) in the middle of a stage), the
 # reverse order fits all of them (profiles/r05_b16_isa_mix.txt).

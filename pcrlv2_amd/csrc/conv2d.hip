@@ -18,10 +18,8 @@
 // Tile 128 x BN (BN = 32/64/128) as in conv_igemm.hip: 4 waves 2x2, LDS double-buffered and XOR-swizzled, register-staged
 // (padding needs zero-fill), two staging register sets.  Epilogue: + bias, store (T or float32, columns >= Nc masked), and the
 // per-tile (sum, sum^2) rows for the training-mode BatchNorm2d that follows.
-#include "common.h"
+#include "internal.h"
 #include "mma_tile.h"
-#include <atomic>
-#include <cstdlib>
 
 namespace {
 
@@ -384,24 +382,6 @@ int conv2d_common(const char* what, int mode, const void* src, const void* wp, c
 
 }  // namespace
 
-// LDS-halo brick kernel (conv_brick.hip, KD = 1)
-bool pcrl_brick_conv2d_eligible(int N, int H, int W, int Ci, int Co, int dtype);
-int64_t pcrl_brick_conv2d_rows(int N, int H, int W);
-int pcrl_brick_conv2d_launch(const void* x, const void* wp, const float* bias, void* y, float* stats, int N, int H, int W, int Ci, int Co, int up,
-                             hipStream_t stream);
-// wide-brick LDS-DMA kernel (conv_brick16.h, MODE 3): 4 images x 8 x 16 pixels per block, no upsampled source
-bool pcrl_brick16_conv2d_eligible(int N, int H, int W, int Ci, int Co, int dtype);
-int64_t pcrl_brick16_conv2d_rows(int N, int H, int W);
-int pcrl_brick16_conv2d_launch(const void* x, const void* wp, const float* bias, void* y, float* stats, int N, int H, int W, int Ci, int Co, hipStream_t stream);
-// right-sized kernel for layers with <= 32 channels on both sides (conv2d_narrow.hip)
-bool pcrl_conv2d_narrow_eligible(int N, int H, int W, int Cs, int Nc, int ks, int dtype);
-int64_t pcrl_conv2d_narrow_rows(int N, int H, int W);
-int pcrl_conv2d_narrow_launch(const void* x, const void* wp, const float* bias, void* y, float* stats, int N, int H, int W, int Cs, int Nc, int ks,
-                              int up, int out_f32, int red2, hipStream_t stream);
-static std::atomic<int> g_conv2d_impl{0};   // 0 = auto (wide brick / brick / narrow kernels where eligible), 1 = always the gather kernel, 2 = auto without the wide brick (tests, A/B)
-static inline bool auto_impl() { return g_conv2d_impl == 0 || g_conv2d_impl == 2; }
-extern "C" void pcrl_debug_set_conv2d_impl(int impl) { g_conv2d_impl = impl; }
-
 extern "C" int64_t pcrl_conv2d_packed_elems(int rows, int taps, int Cs) {
   return (int64_t)((rows + 31) / 32 * 32) * ((taps * Cs + 31) / 32 * 32);
 }
@@ -424,81 +404,96 @@ extern "C" int pcrl_conv2d_pack(const float* w_ref, void* out, int Co, int Ci, i
 
 extern "C" int64_t pcrl_conv2d_stats_rows(int N, int Ho, int Wo) { return ((int64_t)N * Ho * Wo + PCRL_CONV_BM - 1) / PCRL_CONV_BM; }
 
-// which kernel the forward dispatcher picks: 0 gather, 1 LDS-halo brick (4 x 8 x 8), 2 right-sized narrow kernel, 3 wide brick (4 x 8 x 16, LDS-DMA)
+// ---- one routing rule per direction: every query and the launch go through it.  The values are the codes pcrl_conv2d_fwd_kind / _dgrad_kind report. ----
+// LDS-halo brick kernel (conv_brick.hip, KD = 1); right-sized kernel for layers with <= 32 channels on both sides (conv2d_narrow.hip); wide-brick LDS-DMA
+// kernel (conv_brick16.h, MODE 3: 4 images x 8 x 16 pixels per block, no upsampled source).
+enum Conv2dRoute { CONV2D_GATHER = 0, CONV2D_BRICK8 = 1, CONV2D_NARROW = 2, CONV2D_BRICK16 = 3 };
+// `same`: the output has the extents (H, W) the kernels tile, `wide_ok` / `brick_ok`: what else the two brick kernels need of the call.
 // The 32 -> 32 channel layers (decoder block 3 at 256^2) go to the right-sized narrow kernel rather than the brick kernel: 204-219 -> 168 us per
 // launch on the same box once the narrow kernel runs two waves per SIMD (PCRL_OCC2).
-static bool narrow_first(int Cs, int Nc) { return Cs <= 32 && Nc <= 32; }
-static int conv2d_fwd_kind(int N, int Ho, int Wo, int CiP, int Co, int KH, int KW, int stride, int pad, int out_f32, int dtype, int up) {
-  if (auto_impl() && narrow_first(CiP, Co) && KH == KW && (KH == 1 || KH == 3) && stride == 1 && pad == (KH - 1) / 2 && pcrl_conv2d_narrow_eligible(N, Ho, Wo, CiP, Co, KH, dtype))
-    return 2;
-  if (g_conv2d_impl == 0 && KH == 3 && KW == 3 && stride == 1 && pad == 1 && !out_f32 && !up && pcrl_brick16_conv2d_eligible(N, Ho, Wo, CiP, Co, dtype)) return 3;
-  if (auto_impl() && KH == 3 && KW == 3 && stride == 1 && pad == 1 && !out_f32 && pcrl_brick_conv2d_eligible(N, Ho, Wo, CiP, Co, dtype)) return 1;
-  if (auto_impl() && KH == KW && (KH == 1 || KH == 3) && stride == 1 && pad == (KH - 1) / 2 && pcrl_conv2d_narrow_eligible(N, Ho, Wo, CiP, Co, KH, dtype))
-    return 2;
-  return 0;
+static Conv2dRoute conv2d_route(int N, int H, int W, int Cs, int Nc, int KH, int KW, int stride, int pad, bool same, bool wide_ok, bool brick_ok, int dtype) {
+  const int impl = g_hooks.conv2d_impl;
+  if ((impl != 0 && impl != 2) || !same) return CONV2D_GATHER;
+  const bool k3 = KH == 3 && KW == 3 && stride == 1 && pad == 1;
+  const bool narrow = KH == KW && (KH == 1 || KH == 3) && stride == 1 && pad == (KH - 1) / 2 && pcrl_conv2d_narrow_eligible(N, H, W, Cs, Nc, KH, dtype);
+  if (narrow && Cs <= 32 && Nc <= 32) return CONV2D_NARROW;
+  if (impl == 0 && k3 && wide_ok && pcrl_brick16_conv2d_eligible(N, H, W, Cs, Nc, dtype)) return CONV2D_BRICK16;
+  if (k3 && brick_ok && pcrl_brick_conv2d_eligible(N, H, W, Cs, Nc, dtype)) return CONV2D_BRICK8;
+  return narrow ? CONV2D_NARROW : CONV2D_GATHER;
 }
-// rows of [Co][2] statistics the forward WRITES for this geometry (the gather kernel: one per 128 output pixels; the brick kernel: one per
-// 256-pixel brick; the narrow kernel: one per block) -- what the caller hands to pcrl_bn_finalize
+// the forward's output extents (the source is the nearest x2 upsample of the input where up != 0) and its route
+struct Conv2dFwd {
+  int Ho, Wo;
+  Conv2dRoute route;
+};
+static Conv2dFwd conv2d_fwd_route(int N, int Hi, int Wi, int CiP, int Co, int KH, int KW, int stride, int pad, int up, int out_f32, int dtype) {
+  const int Ho = ((up ? 2 * Hi : Hi) + 2 * pad - KH) / stride + 1, Wo = ((up ? 2 * Wi : Wi) + 2 * pad - KW) / stride + 1;
+  return Conv2dFwd{Ho, Wo, conv2d_route(N, Ho, Wo, CiP, Co, KH, KW, stride, pad, true, !out_f32 && !up, !out_f32, dtype)};
+}
+static Conv2dRoute conv2d_dgrad_route(int N, int Hi, int Wi, int Ci, int Ho, int Wo, int CoP, int KH, int KW, int stride, int pad, int dtype) {
+  return conv2d_route(N, Hi, Wi, CoP, Ci, KH, KW, stride, pad, Hi == Ho && Wi == Wo, true, true, dtype);
+}
+// rows of [Co][2] statistics a route WRITES (the gather kernel: one per 128 output pixels; the brick kernels: one per brick; the narrow kernel: one per block)
+static int64_t conv2d_route_rows(Conv2dRoute route, int N, int Ho, int Wo) {
+  switch (route) {
+    case CONV2D_BRICK16: return pcrl_brick16_conv2d_rows(N, Ho, Wo);
+    case CONV2D_BRICK8: return pcrl_brick_conv2d_rows(N, Ho, Wo);
+    case CONV2D_NARROW: return pcrl_conv2d_narrow_rows(N, Ho, Wo);
+    case CONV2D_GATHER: break;
+  }
+  return pcrl_conv2d_stats_rows(N, Ho, Wo);
+}
+// rows of statistics the forward writes for this geometry -- what the caller hands to pcrl_bn_finalize
 extern "C" int64_t pcrl_conv2d_fwd_stats_rows(int N, int Hi, int Wi, int CiP, int Co, int KH, int KW, int stride, int pad, int up, int out_f32, int dtype) {
-  const int Hl = up ? 2 * Hi : Hi, Wl = up ? 2 * Wi : Wi;
-  const int Ho = (Hl + 2 * pad - KH) / stride + 1, Wo = (Wl + 2 * pad - KW) / stride + 1;
-  const int kind = conv2d_fwd_kind(N, Ho, Wo, CiP, Co, KH, KW, stride, pad, out_f32, dtype, up);
-  return kind == 3 ? pcrl_brick16_conv2d_rows(N, Ho, Wo) : kind == 1 ? pcrl_brick_conv2d_rows(N, Ho, Wo) : kind == 2 ? pcrl_conv2d_narrow_rows(N, Ho, Wo) : pcrl_conv2d_stats_rows(N, Ho, Wo);
+  const Conv2dFwd f = conv2d_fwd_route(N, Hi, Wi, CiP, Co, KH, KW, stride, pad, up, out_f32, dtype);
+  return conv2d_route_rows(f.route, N, f.Ho, f.Wo);
 }
 
-// which kernel pcrl_conv2d_fwd / pcrl_conv2d_dgrad run for a geometry: 0 gather implicit GEMM, 1 LDS-halo brick kernel, 2 right-sized narrow kernel
-// (bench.py's roofline classification; no launch)
+// which kernel pcrl_conv2d_fwd / pcrl_conv2d_dgrad run for a geometry: 0 gather implicit GEMM, 1 LDS-halo brick kernel, 2 right-sized narrow kernel,
+// 3 wide brick (bench.py's roofline classification; no launch)
 extern "C" int64_t pcrl_conv2d_fwd_kind(int N, int Hi, int Wi, int CiP, int Co, int KH, int KW, int stride, int pad, int up, int out_f32, int dtype) {
-  const int Hl = up ? 2 * Hi : Hi, Wl = up ? 2 * Wi : Wi;
-  const int Ho = (Hl + 2 * pad - KH) / stride + 1, Wo = (Wl + 2 * pad - KW) / stride + 1;
-  return conv2d_fwd_kind(N, Ho, Wo, CiP, Co, KH, KW, stride, pad, out_f32, dtype, up);
+  return conv2d_fwd_route(N, Hi, Wi, CiP, Co, KH, KW, stride, pad, up, out_f32, dtype).route;
 }
 extern "C" int64_t pcrl_conv2d_dgrad_kind(int N, int Hi, int Wi, int Ci, int Ho, int Wo, int CoP, int KH, int KW, int stride, int pad, int dtype) {
-  if (auto_impl() && narrow_first(CoP, Ci) && KH == KW && (KH == 1 || KH == 3) && stride == 1 && pad == (KH - 1) / 2 && Hi == Ho && Wi == Wo &&
-      pcrl_conv2d_narrow_eligible(N, Hi, Wi, CoP, Ci, KH, dtype))
-    return 2;
-  if (g_conv2d_impl == 0 && KH == 3 && KW == 3 && stride == 1 && pad == 1 && Hi == Ho && Wi == Wo && pcrl_brick16_conv2d_eligible(N, Hi, Wi, CoP, Ci, dtype)) return 3;
-  if (auto_impl() && KH == 3 && KW == 3 && stride == 1 && pad == 1 && Hi == Ho && Wi == Wo && pcrl_brick_conv2d_eligible(N, Hi, Wi, CoP, Ci, dtype)) return 1;
-  if (auto_impl() && KH == KW && (KH == 1 || KH == 3) && stride == 1 && pad == (KH - 1) / 2 && Hi == Ho && Wi == Wo &&
-      pcrl_conv2d_narrow_eligible(N, Hi, Wi, CoP, Ci, KH, dtype))
-    return 2;
-  return 0;
+  return conv2d_dgrad_route(N, Hi, Wi, Ci, Ho, Wo, CoP, KH, KW, stride, pad, dtype);
 }
 
 // stats_rows: rows the caller allocated for stats_partial (>= pcrl_conv2d_fwd_stats_rows(...); rows beyond the written ones are zero-filled)
 extern "C" int pcrl_conv2d_fwd(const void* x, const void* wp, const float* bias, void* y, float* stats_partial, int64_t stats_rows, int N, int Hi, int Wi,
                                int CiP, int Co, int KH, int KW, int stride, int pad, int up, int out_f32, int dtype, pcrl_stream_t stream) {
-  const int Hl = up ? 2 * Hi : Hi, Wl = up ? 2 * Wi : Wi;
-  const int Ho = (Hl + 2 * pad - KH) / stride + 1, Wo = (Wl + 2 * pad - KW) / stride + 1;
-  int kind = (x && wp) ? conv2d_fwd_kind(N, Ho, Wo, CiP, Co, KH, KW, stride, pad, out_f32, dtype, up) : 0;
+  const Conv2dFwd f = conv2d_fwd_route(N, Hi, Wi, CiP, Co, KH, KW, stride, pad, up, out_f32, dtype);
+  const int Ho = f.Ho, Wo = f.Wo;
+  const Conv2dRoute kind = (x && wp) ? f.route : CONV2D_GATHER;
   if (!y) {
     // y = NULL: the per-row statistics only -- a deep-supervision head's convolution whose map nothing reads runs for its BatchNorm's running
     // statistics alone (pcrlv2_model.py:103-106 / train_2d.py:143-168).  Served by the narrow kernel (pcrl_conv2d_fwd_stats_only_ok).
-    PCRL_REQUIRE(x && wp && stats_partial && kind == 2, "conv2d_fwd: y = NULL (statistics only) is not available for this geometry (pcrl_conv2d_fwd_stats_only_ok)");
+    PCRL_REQUIRE(x && wp && stats_partial && kind == CONV2D_NARROW, "conv2d_fwd: y = NULL (statistics only) is not available for this geometry (pcrl_conv2d_fwd_stats_only_ok)");
   }
   if (stats_partial) {
-    const int64_t rw = kind == 3 ? pcrl_brick16_conv2d_rows(N, Ho, Wo) : kind == 1 ? pcrl_brick_conv2d_rows(N, Ho, Wo) : kind == 2 ? pcrl_conv2d_narrow_rows(N, Ho, Wo) : pcrl_conv2d_stats_rows(N, Ho, Wo);
+    const int64_t rw = conv2d_route_rows(kind, N, Ho, Wo);
     PCRL_REQUIRE(stats_rows >= rw, "conv2d_fwd: %lld statistics rows allocated, %lld needed (pcrl_conv2d_fwd_stats_rows)", (long long)stats_rows, (long long)rw);
     if (stats_rows > rw) (void)hipMemsetAsync(stats_partial + rw * Co * 2, 0, (size_t)(stats_rows - rw) * Co * 2 * sizeof(float), as_stream(stream));
   }
-  if (kind == 3) return pcrl_brick16_conv2d_launch(x, wp, bias, y, stats_partial, N, Ho, Wo, CiP, Co, as_stream(stream));
-  if (kind == 1) return pcrl_brick_conv2d_launch(x, wp, bias, y, stats_partial, N, Ho, Wo, CiP, Co, up, as_stream(stream));
-  if (kind == 2) return pcrl_conv2d_narrow_launch(x, wp, bias, y, stats_partial, N, Ho, Wo, CiP, Co, KH, up, out_f32, 0, as_stream(stream));
+  switch (kind) {
+    case CONV2D_BRICK16: return pcrl_brick16_conv2d_launch(x, wp, bias, y, stats_partial, N, Ho, Wo, CiP, Co, as_stream(stream));
+    case CONV2D_BRICK8: return pcrl_brick_conv2d_launch(x, wp, bias, y, stats_partial, N, Ho, Wo, CiP, Co, up, as_stream(stream));
+    case CONV2D_NARROW: return pcrl_conv2d_narrow_launch(x, wp, bias, y, stats_partial, N, Ho, Wo, CiP, Co, KH, up, out_f32, 0, as_stream(stream));
+    case CONV2D_GATHER: break;
+  }
   return conv2d_common("conv2d_fwd", C2_FWD, x, wp, bias, y, stats_partial, N, Hi, Wi, CiP, Ho, Wo, Co, KH, KW, stride, pad, up, out_f32, dtype,
                        as_stream(stream));
 }
 
 extern "C" int64_t pcrl_conv2d_fwd_stats_only_ok(int N, int Hi, int Wi, int CiP, int Co, int KH, int KW, int stride, int pad, int up, int out_f32, int dtype) {
-  const int Hl = up ? 2 * Hi : Hi, Wl = up ? 2 * Wi : Wi;
-  const int Ho = (Hl + 2 * pad - KH) / stride + 1, Wo = (Wl + 2 * pad - KW) / stride + 1;
-  return conv2d_fwd_kind(N, Ho, Wo, CiP, Co, KH, KW, stride, pad, out_f32, dtype, up) == 2 ? 1 : 0;
+  return conv2d_fwd_route(N, Hi, Wi, CiP, Co, KH, KW, stride, pad, up, out_f32, dtype).route == CONV2D_NARROW;
 }
 
 // Data gradient of a 3x3 / stride 1 / pad 1 convolution that read its input through the nearest x2 upsample (decoder conv1,
 // models/pcrlv2_model.py:114), WITH the upsample's backward: dx[N][Hc][Wc][Ci] = 2 x 2 block sums of the fine-resolution data gradient,
 // which is never stored.  Available (pcrl_conv2d_dgrad_up_ok) where the right-sized narrow kernel takes the fine-resolution problem.
 extern "C" int64_t pcrl_conv2d_dgrad_up_ok(int N, int Hc, int Wc, int Ci, int CoP, int dtype) {
-  return (auto_impl() && pcrl_conv2d_narrow_eligible(N, 2 * Hc, 2 * Wc, CoP, Ci, 3, dtype)) ? 1 : 0;
+  const int impl = g_hooks.conv2d_impl;
+  return (impl == 0 || impl == 2) && pcrl_conv2d_narrow_eligible(N, 2 * Hc, 2 * Wc, CoP, Ci, 3, dtype);
 }
 extern "C" int pcrl_conv2d_dgrad_up(const void* dy, const void* wp_dgrad, void* dx, int N, int Hc, int Wc, int Ci, int CoP, int dtype, pcrl_stream_t stream) {
   PCRL_REQUIRE(dy && wp_dgrad && dx, "conv2d_dgrad_up: null pointer");
@@ -509,25 +504,20 @@ extern "C" int pcrl_conv2d_dgrad_up(const void* dy, const void* wp_dgrad, void* 
 // dx[N][Hi][Wi][Ci] from dy[N][Ho][Wo][CoP]; (Ho, Wo) are the forward output dims of the (Hi, Wi) input.
 extern "C" int pcrl_conv2d_dgrad(const void* dy, const void* wp_dgrad, void* dx, int N, int Hi, int Wi, int Ci, int Ho, int Wo, int CoP, int KH,
                                  int KW, int stride, int pad, int dtype, pcrl_stream_t stream) {
-  if (g_conv2d_impl == 0 && dy && wp_dgrad && dx && pcrl_conv2d_dgrad_kind(N, Hi, Wi, Ci, Ho, Wo, CoP, KH, KW, stride, pad, dtype) == 3)
-    return pcrl_brick16_conv2d_launch(dy, wp_dgrad, nullptr, dx, nullptr, N, Hi, Wi, CoP, Ci, as_stream(stream));
-  if (auto_impl() && KH == 3 && KW == 3 && stride == 1 && pad == 1 && dy && wp_dgrad && dx && Hi == Ho && Wi == Wo &&
-      pcrl_brick_conv2d_eligible(N, Hi, Wi, CoP, Ci, dtype) && pcrl_conv2d_dgrad_kind(N, Hi, Wi, Ci, Ho, Wo, CoP, KH, KW, stride, pad, dtype) == 1)
-    return pcrl_brick_conv2d_launch(dy, wp_dgrad, nullptr, dx, nullptr, N, Hi, Wi, CoP, Ci, 0, as_stream(stream));
-  if (auto_impl() && KH == KW && (KH == 1 || KH == 3) && stride == 1 && pad == (KH - 1) / 2 && dy && wp_dgrad && dx && Hi == Ho && Wi == Wo &&
-      pcrl_conv2d_narrow_eligible(N, Hi, Wi, CoP, Ci, KH, dtype))
-    return pcrl_conv2d_narrow_launch(dy, wp_dgrad, nullptr, dx, nullptr, N, Hi, Wi, CoP, Ci, KH, 0, 0, 0, as_stream(stream));
+  switch ((dy && wp_dgrad && dx) ? conv2d_dgrad_route(N, Hi, Wi, Ci, Ho, Wo, CoP, KH, KW, stride, pad, dtype) : CONV2D_GATHER) {   // null pointers: reported below
+    case CONV2D_BRICK16: return pcrl_brick16_conv2d_launch(dy, wp_dgrad, nullptr, dx, nullptr, N, Hi, Wi, CoP, Ci, as_stream(stream));
+    case CONV2D_BRICK8: return pcrl_brick_conv2d_launch(dy, wp_dgrad, nullptr, dx, nullptr, N, Hi, Wi, CoP, Ci, 0, as_stream(stream));
+    case CONV2D_NARROW: return pcrl_conv2d_narrow_launch(dy, wp_dgrad, nullptr, dx, nullptr, N, Hi, Wi, CoP, Ci, KH, 0, 0, 0, as_stream(stream));
+    case CONV2D_GATHER: break;
+  }
   return conv2d_common("conv2d_dgrad", C2_DGRAD, dy, wp_dgrad, nullptr, dx, nullptr, N, Ho, Wo, CoP, Hi, Wi, Ci, KH, KW, stride, pad, 0, 0, dtype,
                        as_stream(stream));
 }
 
 // ---- 3x3 / stride 1 / pad 1 data gradient + first pass of the BatchNorm backward of the layer below (conv_brick16_bnr.hip) ----
-int pcrl_brick16_dgrad2d_bnred_launch(const void* dy, const void* wp, void* dx, const void* bn_y, const float* scale, const float* shift, const float* mean,
-                                      const float* rstd, float* partial, int N, int H, int W, int Ci, int Co, hipStream_t stream);
 extern "C" int64_t pcrl_conv2d_dgrad_bnred_rows(int N, int H, int W, int Ci, int CoP, int act, int dtype) {
-  static const bool off = [] { const char* e = getenv("PCRL_DGRAD_BNRED"); return e && e[0] == '0'; }();   // A/B switch (shared with the 3D path)
-  if (off || act != PCRL_ACT_RELU || N <= 0 || H <= 0 || W <= 0 || Ci <= 0 || CoP <= 0) return 0;
-  return pcrl_conv2d_dgrad_kind(N, H, W, Ci, H, W, CoP, 3, 3, 1, 1, dtype) == 3 ? pcrl_brick16_conv2d_rows(N, H, W) : 0;
+  if (pcrl_env().dgrad_bnred_off || act != PCRL_ACT_RELU || N <= 0 || H <= 0 || W <= 0 || Ci <= 0 || CoP <= 0) return 0;
+  return conv2d_dgrad_route(N, H, W, Ci, H, W, CoP, 3, 3, 1, 1, dtype) == CONV2D_BRICK16 ? pcrl_brick16_conv2d_rows(N, H, W) : 0;
 }
 extern "C" int pcrl_conv2d_dgrad_bnred(const void* dy, const void* wp_dgrad, void* dx, const void* bn_y, const float* scale, const float* shift,
                                        const float* mean, const float* rstd, float* partial, int N, int H, int W, int Ci, int CoP, int act, int dtype,

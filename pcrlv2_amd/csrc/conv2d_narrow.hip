@@ -12,7 +12,7 @@
 // Wave = 64 pixels (two patch rows) x NF * 16 output channels.  Epilogue: + bias, bf16 or float32 store (columns >= Nc masked),
 // one (sum, sum^2) statistics row per BLOCK for the BatchNorm2d that follows (see the kernel's comment for the round-4 form).  The stride-1 data gradient is the same kernel
 // on the tap-flipped packed weights.
-#include "common.h"
+#include "internal.h"
 
 #ifndef NARROW_TRANSPOSED
 #define NARROW_TRANSPOSED 1

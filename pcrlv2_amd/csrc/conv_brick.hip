@@ -15,7 +15,7 @@
 // LDS: halo 960 rows (w pitch padded to 16, bank-conflict-free for every tap offset) x 64 B = 60 KiB, single buffer --
 //      the next chunk is prefetched into registers during the last tap row -- + one weight stage (3 taps x 64 x 64 B =
 //      12 KiB, next stage prefetched into registers) -> 72 KiB, two blocks per CU.
-#include "common.h"
+#include "internal.h"
 
 // (Measured in round 4, not kept, removed: transposed MFMAs (D = W * X^T) so that a lane holds four consecutive channels of one voxel and the epilogue
 // issues 16 eight-byte stores instead of 64 two-byte ones -- 44.7 ms against 43.6 on the C5 step: an eight-byte store of that layout touches 16
@@ -23,7 +23,6 @@
 #ifndef BRICK_ABL
 #define BRICK_ABL 0   // timing ablations (wrong results): bit 0 no output stores, bit 1 no global loads in front of the first stage
 #endif
-#include <atomic>
 #include <mutex>
 
 namespace {
@@ -455,9 +454,6 @@ bool pcrl_brick_conv_eligible(int N, int D, int H, int W, int Ci, int Co, int dt
 }
 int64_t pcrl_brick_conv_rows(int N, int D, int H, int W) { return (int64_t)N * D * H * W / BRICK; }
 
-static std::atomic<int> g_brick_ymap{1};
-void pcrl_brick_conv_set_ymap(int on) { g_brick_ymap = on; }
-
 int pcrl_brick_conv_launch(const void* x, const void* wp, const float* bias, void* y, float* stats,
                            int N, int D, int H, int W, int Ci, int Co, hipStream_t stream) {
   constexpr int HB = BrickGeom<3>::HALO_BYTES;
@@ -476,7 +472,7 @@ int pcrl_brick_conv_launch(const void* x, const void* wp, const float* bias, voi
   // few bricks (the 8 x 8 x 4 level: 32 at b = 32): 32-channel tiles double the number of blocks (128 -> 256 for 256 output channels)
   const int BN = (Co % 64 == 0 && (int64_t)bricks * (Co / 64) > 192) ? 64 : 32, ny = Co / BN;
   dim3 grid(bricks, ny);
-  if (g_brick_ymap && ny > 1 && (uint64_t)bricks * ny < (1u << 31)) {
+  if (g_hooks.brick_ymap && ny > 1 && (uint64_t)bricks * ny < (1u << 31)) {
     p.ny = ny;
     grid = dim3(bricks * ny);
   }

@@ -38,8 +38,7 @@
 // blocks (eight waves) per CU.  The next chunk's halo is requested as soon as every wave holds the last fragments of the current one
 // (first barrier of the chunk's last stage) and lands under that stage's remaining MFMAs and the co-resident block's work.
 #pragma once
-#include "common.h"
-#include <atomic>
+#include "internal.h"
 #include <mutex>
 
 namespace {
@@ -690,7 +689,3 @@ inline int launch16(Brick16Params p, dim3 grid, hipStream_t stream, const char* 
 
 
 }  // namespace
-
-// ---- internal interface (conv_brick16.hip) ----
-bool pcrl_brick16_conv_eligible(int N, int D, int H, int W, int Ci, int Co, int dtype);
-int64_t pcrl_brick16_conv_rows(int N, int D, int H, int W);

@@ -1,17 +1,10 @@
 // Plain 3x3x3 instantiations of the wide-brick convolution kernel (conv_brick16.h) and the dispatcher's interface to them.
 #include "conv_brick16.h"
 
-namespace {
-std::atomic<int> g_brick16_on{1};
-std::atomic<int> g_brick16_planes{-1};   // -1: the default rule (4-plane bricks); 0: 4-plane bricks only; 2: 8-plane bricks wherever they tile
-}  // namespace
-
 // ---- internal interface used by conv_igemm.hip's dispatcher -------------------------------------------------------
-void pcrl_brick16_set(int on) { g_brick16_on = on; }
-void pcrl_brick16_set_planes(int mode) { g_brick16_planes = mode; }
 bool pcrl_brick16_conv_eligible(int N, int D, int H, int W, int Ci, int Co, int dtype) {
   // the halo plan addresses a brick's source rows by 32-bit offsets from its first halo voxel (up to ten planes of 2 Ci H W bytes), a weight row by a 32-bit offset
-  return g_brick16_on && dtype == PCRL_BF16 && brick16_perm(D, H, W) != 0 && Ci % 32 == 0 && Co % 32 == 0 && (int64_t)N * D * H * W < ((int64_t)1 << 29) &&
+  return g_hooks.brick16_on && dtype == PCRL_BF16 && brick16_perm(D, H, W) != 0 && Ci % 32 == 0 && Co % 32 == 0 && (int64_t)N * D * H * W < ((int64_t)1 << 29) &&
          (int64_t)20 * Ci * H * W < ((int64_t)1 << 31) && (int64_t)54 * Ci * Co < ((int64_t)1 << 32);
 }
 int64_t pcrl_brick16_conv_rows(int N, int D, int H, int W) { return (int64_t)N * D * H * W / (TD * TH * TW); }
@@ -28,7 +21,7 @@ int pcrl_brick16_conv_launch(const void* x, const void* wp, const float* bias, v
   // 1 363 vs 1 225 TFLOP/s, 256->128 1 537 vs 1 480, 128->128 1 492 vs 1 435, the 16x16x8 decoder layers within 1 %; one pass over the model's layers 4.28 vs
   // 4.35 ms) -- what the 8-plane brick saved was halo REQUEST ISSUE, which the plan made cheap.  Off; the instantiation stays behind the test hook
   // (pcrl_debug_set_conv_impl 5: the round-4 rule, 6: every eligible shape), bit-identical to the 4-plane form.
-  const int nw8_mode = g_brick16_planes >= 0 ? (int)g_brick16_planes : 0;
+  const int planes = g_hooks.brick16_planes, nw8_mode = planes >= 0 ? planes : 0;
   int64_t bricks = pcrl_brick16_conv_rows(N, D, H, W);
   const bool nw8 = nw8_mode > 0 && BN == 64 && D % 8 == 0 && (nw8_mode == 2 || (ny >= 2 && (bricks / 2) * ny >= 256));
   if (nw8) bricks /= 2;
@@ -46,7 +39,7 @@ int pcrl_brick16_conv_launch(const void* x, const void* wp, const float* bias, v
 // ---- 2D path (MODE 3): 3x3 / stride 1 / pad 1 convolution of [N][H][W][Ci] images, forward or data gradient (conv2d.hip's dispatcher) ----
 // The image index is the brick's d axis (4 images per brick); wp: packed [Co][9][Ci] (pcrl_conv2d_pack); stats [bricks][Co][2] or null.
 bool pcrl_brick16_conv2d_eligible(int N, int H, int W, int Ci, int Co, int dtype) {
-  return g_brick16_on && dtype == PCRL_BF16 && N % TD == 0 && brick16_perm(N, H, W) != 0 && Ci % 32 == 0 && Co % 32 == 0 &&
+  return g_hooks.brick16_on && dtype == PCRL_BF16 && N % TD == 0 && brick16_perm(N, H, W) != 0 && Ci % 32 == 0 && Co % 32 == 0 &&
          (int64_t)N * H * W < ((int64_t)1 << 29) && (int64_t)20 * Ci * H * W < ((int64_t)1 << 31) && (int64_t)18 * Ci * Co < ((int64_t)1 << 32);
 }
 int64_t pcrl_brick16_conv2d_rows(int N, int H, int W) { return (int64_t)N * H * W / (TD * TH * TW); }

@@ -10,7 +10,6 @@
 // fixed-order fp64 sum over the brick rows).
 #include "conv_brick16.h"
 
-bool pcrl_brick16_conv_eligible(int N, int D, int H, int W, int Ci, int Co, int dtype);   // conv_brick16.hip
 
 // partial: [pcrl_brick16_conv_rows(N, D, H, W)][Co][2]; scale, shift, mean, rstd: Co floats each (the layer below's pcrl_bn_finalize outputs)
 int pcrl_brick16_dgrad_bnred_launch(const void* dy, const void* wp, void* dx, const void* bn_y, const float* scale, const float* shift, const float* mean,

@@ -6,7 +6,7 @@
 // Scalar fields (x of the first layer, y/dy of the heads) are float32 [M]; C-channel tensors are NDHWC
 // in the activation dtype, accessed as 16-byte channel vectors.  The weight gradients of these layers are MFMA GEMMs
 // (conv_wgrad.hip, via an im2col of the scalar operand).
-#include "common.h"
+#include "internal.h"
 #include <cstdlib>
 
 namespace {
@@ -469,9 +469,8 @@ int pow2_floor(int v) {
 
 }  // namespace
 
-int pcrl_debug_conv_impl();   // conv_igemm.hip: 0 = auto
 static bool c1_brick_ok(int D, int H, int W, int dtype) {
-  return pcrl_debug_conv_impl() == 0 && dtype == PCRL_BF16 && D % 4 == 0 && H % 8 == 0 && W % 8 == 0;
+  return g_hooks.conv_impl == 0 && dtype == PCRL_BF16 && D % 4 == 0 && H % 8 == 0 && W % 8 == 0;
 }
 extern "C" int64_t pcrl_conv3d_k3_c1_stats_rows(int N, int D, int H, int W, int Co, int dtype) {
   (void)Co;
@@ -532,15 +531,12 @@ static int to1_check(const char* what, int C, int taps, int dtype) {
   return 0;
 }
 
-int pcrl_pointwise_planes_launch(const void* x, const void* wt, float* z, int64_t M, int C, int dtype, hipStream_t stream);
-// LDS-halo brick kernel (conv_to1_brick.hip)
-bool pcrl_to1_brick_eligible(int N, int D, int H, int W, int C, int taps, int dtype);
-int64_t pcrl_to1_brick_rows(int N, int D, int H, int W);
-int pcrl_to1_brick_launch(const void* x, const float* w_ref, const float* bias, float* y, float* stats, void* ws, size_t ws_bytes, int N, int D, int H,
-                          int W, int C, hipStream_t stream);
-
+// the LDS-halo brick kernel (conv_to1_brick.hip) takes this shape
+static bool to1_brick_route(int N, int D, int H, int W, int C, int taps, int dtype) {
+  return g_hooks.conv_impl == 0 && pcrl_to1_brick_eligible(N, D, H, W, C, taps, dtype);
+}
 extern "C" int64_t pcrl_conv3d_to1_stats_rows(int N, int D, int H, int W, int C, int taps, int dtype) {
-  if (pcrl_debug_conv_impl() == 0 && pcrl_to1_brick_eligible(N, D, H, W, C, taps, dtype)) return pcrl_to1_brick_rows(N, D, H, W);
+  if (to1_brick_route(N, D, H, W, C, taps, dtype)) return pcrl_to1_brick_rows(N, D, H, W);
   return ((int64_t)N * D * H * W + TO1_VOX - 1) / TO1_VOX;
 }
 
@@ -554,7 +550,7 @@ extern "C" int pcrl_conv3d_to1_fwd(const void* x, const float* w_ref, const floa
                                    pcrl_stream_t stream) {
   if (int e = to1_check("conv3d_to1_fwd", C, taps, dtype)) return e;
   PCRL_REQUIRE(x && w_ref && y, "conv3d_to1_fwd: null pointer");
-  if (pcrl_debug_conv_impl() == 0 && pcrl_to1_brick_eligible(N, D, H, W, C, taps, dtype))
+  if (to1_brick_route(N, D, H, W, C, taps, dtype))
     return pcrl_to1_brick_launch(x, w_ref, bias, y, stats_partial, ws, ws_bytes, N, D, H, W, C, as_stream(stream));
   const Dims g{N, D, H, W};
   const int64_t M = (int64_t)N * D * H * W;

@@ -18,10 +18,8 @@
 // Epilogue: + bias, store, and per-tile per-channel (sum, sum of squares) from the fp32
 // accumulators for the training-mode BatchNorm that follows every conv (no atomics: one partial
 // row per tile, reduced in fixed order by bn_finalize).
-#include "common.h"
+#include "internal.h"
 #include "mma_tile.h"
-#include <atomic>
-#include <cstdlib>
 
 namespace {
 
@@ -557,48 +555,26 @@ static SplitPlan splitk_plan(int64_t M, int Ci, int Co, int taps = 27) {
 
 }  // namespace
 
-// LDS-halo brick kernel (conv_brick.hip)
-bool pcrl_brick_conv_eligible(int N, int D, int H, int W, int Ci, int Co, int dtype);
-int64_t pcrl_brick_conv_rows(int N, int D, int H, int W);
-int pcrl_brick_conv_launch(const void* x, const void* wp, const float* bias, void* y, float* stats,
-                           int N, int D, int H, int W, int Ci, int Co, hipStream_t stream);
-
-// wide-brick kernel (conv_brick16.hip): W % 16 == 0
-bool pcrl_brick16_conv_eligible(int N, int D, int H, int W, int Ci, int Co, int dtype);
-int64_t pcrl_brick16_conv_rows(int N, int D, int H, int W);
-int pcrl_brick16_conv_launch(const void* x, const void* wp, const float* bias, void* y, float* stats,
-                             int N, int D, int H, int W, int Ci, int Co, hipStream_t stream);
-void pcrl_brick16_set(int on);
-void pcrl_brick16_set_planes(int mode);
-
-bool pcrl_convt_up2_eligible(int Ci, int Co, int dtype);   // conv_up2.hip
-int pcrl_convt_up2_launch(const void* x, const void* wp, const float* bias, void* y, int N, int D, int H, int W, int Ci, int Co,
-                          hipStream_t stream);
-static std::atomic<int> g_conv_impl{0};  // 0 = auto (brick kernel where eligible), 1 = always the gather kernel
-void pcrl_brick_conv_set_ymap(int on);
-// 0 = auto (brick kernel where eligible), 1 = always the gather kernel, 2 = gather kernel without split-K,
-// 3 = brick kernel on its 2-D grid (channel tiles of a brick not co-located), 4 = 4x8x8-brick kernel also where the 4x8x16 one is eligible,
-// 5 / 6 = auto with the wide-brick kernel on 4-plane bricks only / on 8-plane bricks wherever they tile (0: its own rule, conv_brick16.hip)
-extern "C" void pcrl_debug_set_conv_impl(int impl) {
-  g_conv_impl = (impl == 3 || impl == 4 || impl == 5 || impl == 6) ? 0 : impl;
-  pcrl_brick_conv_set_ymap(impl != 3);
-  pcrl_brick16_set(impl == 0 || impl == 5 || impl == 6);
-  pcrl_brick16_set_planes(impl == 5 ? 0 : impl == 6 ? 2 : -1);
+// The kernel family a 3x3x3 convolution of this shape runs on -- the ONE routing rule behind every query and launch below.  The values are the
+// codes pcrl_conv3d_k3_fwd_kernel reports: wide brick (conv_brick16.hip, W % 16 == 0) before 4 x 8 x 8 brick (conv_brick.hip) before gather.
+enum Conv3Route { CONV3_GATHER = 0, CONV3_BRICK8 = 1, CONV3_BRICK16 = 2 };
+static Conv3Route conv3_route(int N, int D, int H, int W, int Ci, int Co, int dtype) {
+  if (g_hooks.conv_impl != 0) return CONV3_GATHER;
+  if (pcrl_brick16_conv_eligible(N, D, H, W, Ci, Co, dtype)) return CONV3_BRICK16;
+  return pcrl_brick_conv_eligible(N, D, H, W, Ci, Co, dtype) ? CONV3_BRICK8 : CONV3_GATHER;
 }
-int pcrl_debug_conv_impl() { return g_conv_impl; }
 
 extern "C" int64_t pcrl_conv3d_k3_stats_rows(int N, int D, int H, int W, int Ci, int Co, int dtype) {
-  if (g_conv_impl == 0 && pcrl_brick16_conv_eligible(N, D, H, W, Ci, Co, dtype)) return pcrl_brick16_conv_rows(N, D, H, W);
-  if (g_conv_impl == 0 && pcrl_brick_conv_eligible(N, D, H, W, Ci, Co, dtype)) return pcrl_brick_conv_rows(N, D, H, W);
+  switch (conv3_route(N, D, H, W, Ci, Co, dtype)) {
+    case CONV3_BRICK16: return pcrl_brick16_conv_rows(N, D, H, W);
+    case CONV3_BRICK8: return pcrl_brick_conv_rows(N, D, H, W);
+    case CONV3_GATHER: break;
+  }
   return ((int64_t)N * D * H * W + PCRL_CONV_BM - 1) / PCRL_CONV_BM;
 }
 
 // informational: which kernel pcrl_conv3d_k3_fwd gives this shape -- 2: wide-brick (conv_brick16.hip), 1: brick (conv_brick.hip), 0: gather
-extern "C" int64_t pcrl_conv3d_k3_fwd_kernel(int N, int D, int H, int W, int Ci, int Co, int dtype) {
-  if (g_conv_impl == 0 && pcrl_brick16_conv_eligible(N, D, H, W, Ci, Co, dtype)) return 2;
-  if (g_conv_impl == 0 && pcrl_brick_conv_eligible(N, D, H, W, Ci, Co, dtype)) return 1;
-  return 0;
-}
+extern "C" int64_t pcrl_conv3d_k3_fwd_kernel(int N, int D, int H, int W, int Ci, int Co, int dtype) { return conv3_route(N, D, H, W, Ci, Co, dtype); }
 
 // Voxel-major rows with per-tile tap skipping (IgemmParams::vmajor) for volumes of at most 8 voxels (the local views' 2^3 level: 8 of 27 taps per
 // voxel).  Measured (tools/conv_probe.py --b 192, same box): 2^3, 256 -> 256 / 256 -> 512 channels 51 -> 28 / 65 -> 43 us; on the 4^3 level (15.6 of
@@ -606,9 +582,8 @@ extern "C" int64_t pcrl_conv3d_k3_fwd_kernel(int N, int D, int H, int W, int Ci,
 // samples (16 KB, cache resident), a voxel-major one from 128 samples -- that level is bound by the gather, not by K, and keeps sample-major rows.
 // PCRL_IGEMM_VMAJOR=0: off; =64: also the volumes of up to 64 voxels (A/B switch).  -> taps a tile walks on average, 0 = off.
 static int conv3_vmajor_taps(int N, int D, int H, int W) {
-  static const int vmax = [] { const char* e = getenv("PCRL_IGEMM_VMAJOR"); return e ? atoi(e) == 1 ? 8 : atoi(e) : 8; }();
   const int64_t V = (int64_t)D * H * W;
-  if (V > vmax || (int64_t)N * V < PCRL_CONV_BM) return 0;
+  if (V > pcrl_env().igemm_vmajor_max || (int64_t)N * V < PCRL_CONV_BM) return 0;
   const double t = (3.0 * D - 2) * (3.0 * H - 2) * (3.0 * W - 2) / (double)V;
   return t < 1 ? 1 : (int)(t + 0.5);
 }
@@ -617,16 +592,17 @@ static int conv3d_k3_fwd_impl(const void* x, const void* wp, const float* bias, 
                              int N, int D, int H, int W, int Ci, int Co, int dtype, pcrl_stream_t stream) {
   if (int e = check_dims("conv3d_k3_fwd", N, D, H, W, Ci, Co)) return e;
   PCRL_REQUIRE(x && wp && y, "conv3d_k3_fwd: null pointer");
-  if (g_conv_impl == 0 && pcrl_brick16_conv_eligible(N, D, H, W, Ci, Co, dtype))
-    return pcrl_brick16_conv_launch(x, wp, bias, y, stats_partial, N, D, H, W, Ci, Co, as_stream(stream));
-  if (g_conv_impl == 0 && pcrl_brick_conv_eligible(N, D, H, W, Ci, Co, dtype))
-    return pcrl_brick_conv_launch(x, wp, bias, y, stats_partial, N, D, H, W, Ci, Co, as_stream(stream));
+  switch (conv3_route(N, D, H, W, Ci, Co, dtype)) {
+    case CONV3_BRICK16: return pcrl_brick16_conv_launch(x, wp, bias, y, stats_partial, N, D, H, W, Ci, Co, as_stream(stream));
+    case CONV3_BRICK8: return pcrl_brick_conv_launch(x, wp, bias, y, stats_partial, N, D, H, W, Ci, Co, as_stream(stream));
+    case CONV3_GATHER: break;
+  }
   const int64_t M = (int64_t)N * D * H * W;
   IgemmParams p{x, wp, bias, y, stats_partial, Dims{N, D, H, W}, M, Ci, Co, 27, nullptr, 0};
   const int vtaps = conv3_vmajor_taps(N, D, H, W);
   p.vmajor = vtaps > 0;
   const SplitPlan sp = splitk_plan(M, Ci, Co, vtaps ? vtaps : 27);
-  if (ws && sp.splits > 1 && g_conv_impl != 2) {
+  if (ws && sp.splits > 1 && g_hooks.conv_impl != 2) {
     PCRL_REQUIRE(ws_bytes >= (int64_t)sp.splits * M * Co * 4, "conv3d_k3_fwd: workspace too small (%lld bytes)", (long long)ws_bytes);
     p.ws = static_cast<float*>(ws);
     p.steps_per_split = sp.steps_per_split;
@@ -651,7 +627,7 @@ extern "C" int pcrl_conv3d_k3_fwd(const void* x, const void* wp, const float* bi
 
 extern "C" int64_t pcrl_conv3d_k3_fwd_ws_bytes(int N, int D, int H, int W, int Ci, int Co, int dtype) {
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || Ci % 32 != 0 || Co % 32 != 0) return 0;
-  if (g_conv_impl == 0 && (pcrl_brick_conv_eligible(N, D, H, W, Ci, Co, dtype) || pcrl_brick16_conv_eligible(N, D, H, W, Ci, Co, dtype))) return 0;
+  if (conv3_route(N, D, H, W, Ci, Co, dtype) != CONV3_GATHER) return 0;
   const int64_t M = (int64_t)N * D * H * W;
   const int vtaps = conv3_vmajor_taps(N, D, H, W);
   const SplitPlan sp = splitk_plan(M, Ci, Co, vtaps ? vtaps : 27);
@@ -664,23 +640,16 @@ extern "C" int pcrl_conv3d_k3_fwd_ws(const void* x, const void* wp, const float*
 }
 
 // ---- inference forward: convolution + eval-mode BatchNorm + activation in one pass (wide-brick: conv_brick16_inf.hip; gather: AFF above) ----
-int pcrl_brick16_conv_affine_launch(const void* x, const void* wp, const float* bias, const float* scale, const float* shift, float act_lo, void* a,
-                                    int N, int D, int H, int W, int Ci, int Co, hipStream_t stream);
-// The route ops.luconv_infer takes -- 2: wide-brick kernel, 1: gather kernel in one pass, 0: conv + apply as two passes, because the unfused convolution
-// of the shape runs on a kernel family without a fused form (4x8x8 bricks, split-K, voxel-major rows).  pcrl_conv3d_k3_fwd_affine itself computes every
-// shape: the wide-brick kernel where eligible, else the gather kernel in one pass.
-static int conv3d_k3_affine_route(int N, int D, int H, int W, int Ci, int Co, int dtype) {
+// Whether ops.luconv_infer takes the fused form: not where the unfused convolution of the shape runs on a kernel family without one (4x8x8 bricks,
+// split-K, voxel-major rows), which then runs conv + apply as two passes.  pcrl_conv3d_k3_fwd_affine itself computes every shape: the wide-brick kernel
+// where conv3_route says so, else the gather kernel in one pass.
+extern "C" int64_t pcrl_conv3d_k3_fwd_affine_fused(int N, int D, int H, int W, int Ci, int Co, int dtype) {
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || Ci % 32 != 0 || Co % 32 != 0) return 0;
   if (dtype != PCRL_BF16 && dtype != PCRL_F32) return 0;
-  if (g_conv_impl == 0 && pcrl_brick16_conv_eligible(N, D, H, W, Ci, Co, dtype)) return 2;
-  if (g_conv_impl == 0 && pcrl_brick_conv_eligible(N, D, H, W, Ci, Co, dtype)) return 0;
-  const int vtaps = conv3_vmajor_taps(N, D, H, W);
-  if (vtaps) return 0;
-  if (g_conv_impl != 2 && splitk_plan((int64_t)N * D * H * W, Ci, Co, 27).splits > 1) return 0;
-  return 1;
-}
-extern "C" int64_t pcrl_conv3d_k3_fwd_affine_fused(int N, int D, int H, int W, int Ci, int Co, int dtype) {
-  return conv3d_k3_affine_route(N, D, H, W, Ci, Co, dtype) != 0;
+  const Conv3Route route = conv3_route(N, D, H, W, Ci, Co, dtype);
+  if (route != CONV3_GATHER) return route == CONV3_BRICK16;
+  if (conv3_vmajor_taps(N, D, H, W)) return 0;
+  return g_hooks.conv_impl == 2 || splitk_plan((int64_t)N * D * H * W, Ci, Co, 27).splits <= 1;
 }
 extern "C" int64_t pcrl_conv3d_k3_fwd_affine_ws_bytes(int N, int D, int H, int W, int Ci, int Co, int dtype) {
   (void)N; (void)D; (void)H; (void)W; (void)Ci; (void)Co; (void)dtype;
@@ -693,9 +662,8 @@ extern "C" int pcrl_conv3d_k3_fwd_affine(const void* x, const void* wp, const fl
   PCRL_REQUIRE(x && wp && scale && shift && a, "conv3d_k3_fwd_affine: null pointer");
   PCRL_REQUIRE(act == PCRL_ACT_RELU || act == PCRL_ACT_NONE, "conv3d_k3_fwd_affine: activation %d has no fused form (ReLU or none)", act);
   PCRL_REQUIRE(dtype == PCRL_BF16 || dtype == PCRL_F32, "conv3d_k3_fwd_affine: bad dtype %d", dtype);
-  const int route = conv3d_k3_affine_route(N, D, H, W, Ci, Co, dtype);
   const float act_lo = act == PCRL_ACT_RELU ? 0.f : -__builtin_inff();
-  if (route == 2) return pcrl_brick16_conv_affine_launch(x, wp, bias, scale, shift, act_lo, a, N, D, H, W, Ci, Co, as_stream(stream));
+  if (conv3_route(N, D, H, W, Ci, Co, dtype) == CONV3_BRICK16) return pcrl_brick16_conv_affine_launch(x, wp, bias, scale, shift, act_lo, a, N, D, H, W, Ci, Co, as_stream(stream));
   IgemmParams p{x, wp, bias, a, nullptr, Dims{N, D, H, W}, (int64_t)N * D * H * W, Ci, Co, 27, nullptr, 0};
   p.vmajor = 0;
   p.aff_scale = scale;
@@ -706,13 +674,9 @@ extern "C" int pcrl_conv3d_k3_fwd_affine(const void* x, const void* wp, const fl
 }
 
 // ---- data gradient + first pass of the BatchNorm backward of the layer below (conv_brick16_bnr.hip) ----
-int pcrl_brick16_dgrad_bnred_launch(const void* dy, const void* wp, void* dx, const void* bn_y, const float* scale, const float* shift, const float* mean,
-                                    const float* rstd, float* partial, int N, int D, int H, int W, int Ci, int Co, hipStream_t stream);
 extern "C" int64_t pcrl_conv3d_k3_dgrad_bnred_rows(int N, int D, int H, int W, int Ci, int Co, int act, int dtype) {
-  static const bool off = [] { const char* e = getenv("PCRL_DGRAD_BNRED"); return e && e[0] == '0'; }();   // A/B switch
-  if (off || act != PCRL_ACT_RELU || N <= 0 || D <= 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0) return 0;
-  if (g_conv_impl == 0 && pcrl_brick16_conv_eligible(N, D, H, W, Ci, Co, dtype)) return pcrl_brick16_conv_rows(N, D, H, W);
-  return 0;
+  if (pcrl_env().dgrad_bnred_off || act != PCRL_ACT_RELU || N <= 0 || D <= 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0) return 0;
+  return conv3_route(N, D, H, W, Ci, Co, dtype) == CONV3_BRICK16 ? pcrl_brick16_conv_rows(N, D, H, W) : 0;
 }
 extern "C" int pcrl_conv3d_k3_dgrad_bnred(const void* dy, const void* wp_dgrad, void* dx, const void* bn_y, const float* scale, const float* shift,
                                           const float* mean, const float* rstd, float* partial, int N, int D, int H, int W, int Ci, int Co, int act,
@@ -728,7 +692,7 @@ extern "C" int pcrl_convt3d_k2s2_fwd(const void* x, const void* wp_fwd, const fl
                                      int N, int D, int H, int W, int Ci, int Co, int dtype, pcrl_stream_t stream) {
   if (int e = check_dims("convt3d_k2s2_fwd", N, D, H, W, Ci, Co)) return e;
   PCRL_REQUIRE(x && wp_fwd && y, "convt3d_k2s2_fwd: null pointer");
-  if (g_conv_impl == 0 && pcrl_convt_up2_eligible(Ci, Co, dtype))
+  if (g_hooks.conv_impl == 0 && pcrl_convt_up2_eligible(Ci, Co, dtype))
     return pcrl_convt_up2_launch(x, wp_fwd, bias, y, N, D, H, W, Ci, Co, as_stream(stream));
   IgemmParams p{x, wp_fwd, bias, y, nullptr, Dims{N, D, H, W}, (int64_t)N * D * H * W, Ci, Co, 1, nullptr, 0};
   return dispatch<GEOM_UP2_FWD>(p, 8, dtype, as_stream(stream));
@@ -766,23 +730,6 @@ int pcrl_upc_fwd_launch(const void* x, const void* wf, const float* bias_tab, vo
   IgemmParams p{x, wf, bias_tab, y0, stats, Dims{N, D, H, W}, (int64_t)N * D * H * W, Ci, Co, 8, nullptr, 0};
   return launch_upc<GEOM_UPC_FWD>(p, 8, dtype, stream);
 }
-bool pcrl_brick16_upc_fwd_eligible(int N, int D, int H, int W, int Ci, int Co, int dtype);   // conv_brick16.hip
-bool pcrl_brick8_upc_fwd_eligible(int N, int D, int H, int W, int Ci, int Co, int dtype);    // conv_brick.hip
-// 0: gather kernel; 1: wide-brick kernel (conv_brick16.hip); 2: 4 x 8 x 8-brick kernel (conv_brick.hip)
-int pcrl_upc_fwd_impl(int N, int D, int H, int W, int Ci, int Co, int dtype) {
-  if (g_conv_impl != 0) return 0;
-  if (pcrl_brick16_upc_fwd_eligible(N, D, H, W, Ci, Co, dtype)) return 1;
-  return pcrl_brick8_upc_fwd_eligible(N, D, H, W, Ci, Co, dtype) ? 2 : 0;
-}
-bool pcrl_upc_fwd_uses_brick(int N, int D, int H, int W, int Ci, int Co, int dtype) { return pcrl_upc_fwd_impl(N, D, H, W, Ci, Co, dtype) != 0; }
-bool pcrl_brick16_upc_dgrad_eligible(int N, int D, int H, int W, int Ci, int Co, int dtype);   // conv_brick16.hip
-bool pcrl_brick8_upc_dgrad_eligible(int N, int D, int H, int W, int Ci, int Co, int dtype);    // conv_brick.hip
-int pcrl_upc_dgrad_impl(int N, int D, int H, int W, int Ci, int Co, int dtype) {
-  if (g_conv_impl != 0) return 0;
-  if (pcrl_brick16_upc_dgrad_eligible(N, D, H, W, Ci, Co, dtype)) return 1;
-  return pcrl_brick8_upc_dgrad_eligible(N, D, H, W, Ci, Co, dtype) ? 2 : 0;
-}
-bool pcrl_upc_dgrad_uses_brick(int N, int D, int H, int W, int Ci, int Co, int dtype) { return pcrl_upc_dgrad_impl(N, D, H, W, Ci, Co, dtype) != 0; }
 // Split-K plan of the composed data gradient on the gather kernel: K = 64 taps x Co / 32 chunks (512 steps at up_tr256) over row tiles that
 // are few on the coarse grids it serves -- the 8 x 8 x 4 grid of up_tr256 (64 tiles x 4 channel tiles = one block per CU, four waves: 319 us,
 // 430 TFLOP/s) and the 2^3 / 4^3 grids of the local views (12 tiles: 287 us, 90 TFLOP/s).  Splits bring the grid to ~4 blocks per CU.

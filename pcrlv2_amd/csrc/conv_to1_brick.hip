@@ -18,7 +18,7 @@
 // block (2 048 scattered loads per block of 256 voxels; 15-30 % of the kernel by ablation).  Now: compact rows, z in two phases
 // (43 KB: three blocks per CU), and the weight tiles packed once per call into the workspace as the LDS image (one 16-byte load
 // per thread and chunk pair).
-#include "common.h"
+#include "internal.h"
 #include <mutex>
 
 namespace {
@@ -240,9 +240,9 @@ bool pcrl_to1_brick_eligible(int N, int D, int H, int W, int C, int taps, int dt
 }
 int64_t pcrl_to1_brick_rows(int N, int D, int H, int W) { return (int64_t)N * (D / TD) * (H / TH) * (W / TW); }
 
-size_t pcrl_to1_brick_ws_bytes(int C) { return (size_t)(C / 32) * 2048; }
+static size_t to1_brick_ws_bytes(int C) { return (size_t)(C / 32) * 2048; }
 
-// ws (optional, pcrl_to1_brick_ws_bytes(C)): receives the packed weight tiles; without it every block converts the weights itself
+// ws (optional, to1_brick_ws_bytes(C)): receives the packed weight tiles; without it every block converts the weights itself
 int pcrl_to1_brick_launch(const void* x, const float* w_ref, const float* bias, float* y, float* stats, void* ws, size_t ws_bytes, int N, int D, int H,
                           int W, int C, hipStream_t stream) {
   const int lds_w = HALO_BYTES + (C / 32) * 2048;
@@ -252,7 +252,7 @@ int pcrl_to1_brick_launch(const void* x, const float* w_ref, const float* bias, 
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(to1_brick_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, HALO_BYTES + 16 * 2048);
   });
   const bf16* img = nullptr;
-  if (ws && ws_bytes >= pcrl_to1_brick_ws_bytes(C)) {
+  if (ws && ws_bytes >= to1_brick_ws_bytes(C)) {
     img = (const bf16*)ws;
     hipLaunchKernelGGL(to1_pack_kernel, dim3((unsigned)((C * 32 + 255) / 256)), dim3(256), 0, stream, w_ref, (bf16*)ws, C);
     if (int e = pcrl_check_launch("to1_pack")) return e;

@@ -14,7 +14,7 @@
 //   * the product is computed TRANSPOSED (A operand = weights, B operand = x), and the weight rows are permuted on their
 //     way into LDS so that D row 4*lg + r of column fragment j is channel 16*lg + 4*j + r: a lane ends up with 16
 //     CONSECUTIVE channels of one output voxel = two 16-byte stores (instead of sixteen 2-byte ones).
-#include "common.h"
+#include "internal.h"
 
 namespace {
 

@@ -15,8 +15,7 @@
 //
 // Block = 64(i) x 64(j) result tile of ONE tap and ONE voxel split; 4 waves as 2x2, each 32x32
 // (2x2 fragments); K-step = 32 voxels, double-buffered register-staged LDS tiles.
-#include "common.h"
-#include <atomic>
+#include "internal.h"
 #include <mutex>
 
 namespace {
@@ -474,15 +473,12 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* __restri
 }
 
 // Timing ablation (tools/double_ablation.py): the non-accumulating second passes are launched this many times (idempotent: same slabs, same output) --
-// what a set of launches costs INSIDE the three-stream step is the step-time difference between 2 and 1.  Default 1.
-static std::atomic<int> g_reduce_repeat{1};
-extern "C" void pcrl_debug_set_reduce_repeat(int n) { g_reduce_repeat = n < 1 ? 1 : n; }
-
+// what a set of launches costs INSIDE the three-stream step is the step-time difference between 2 and 1 (g_hooks.reduce_repeat, default 1).
 // every weight-gradient path ends here (`accumulate`: out += the sum, for gradients gathered over several passes)
 int launch_wgrad_reduce(const float* ws, float* out, int splits, int taps, int Cu, int Cv, int Cv_out, hipStream_t stream, bool accumulate = false) {
   if (taps < 1 || taps > 64) return pcrl_fail(PCRL_EINVAL, "wgrad_reduce: %d taps", taps);
   const int blocks = (int)(((int64_t)Cu * Cv_out + RED_IJ - 1) / RED_IJ);
-  for (int rep = accumulate ? 1 : (int)g_reduce_repeat; rep > 0; --rep)
+  for (int rep = accumulate ? 1 : (int)g_hooks.reduce_repeat; rep > 0; --rep)
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, stream, ws, out, splits, taps, Cu, Cv, Cv_out, accumulate);
   return pcrl_check_launch("wgrad_reduce");
 }
@@ -1159,8 +1155,6 @@ SplitPlan plan_splits(int64_t M, int Cu, int Cv, int taps) {
   return SplitPlan{(int)splits, steps_per * 32};
 }
 
-std::atomic<int> g_wgrad_tr{1};  // bf16 fragment fetch: 1 = ds_read_b64_tr_b16, 0 = scalar LDS reads
-
 template <int GEOM>
 int run_wgrad(const void* u, const void* v, float* dw_ref, void* ws, size_t ws_bytes, Dims g, int Cu, int Cv, int taps,
               int dtype, hipStream_t stream, int Cv_out = -1, Wg2d q = Wg2d{0, 0, 1, 1, 0, 0, 1, 1}) {
@@ -1172,7 +1166,7 @@ int run_wgrad(const void* u, const void* v, float* dw_ref, void* ws, size_t ws_b
   WgradParams p{u, v, (float*)ws, g, M, Cu, Cv, taps, sp.chunk, q};
   dim3 grid((unsigned)(((Cu + 63) / 64) * ((Cv + 63) / 64)), (unsigned)taps, (unsigned)sp.splits);
   if (dtype == PCRL_BF16) {
-    if (g_wgrad_tr) hipLaunchKernelGGL((wgrad_kernel<bf16, GEOM, true>), grid, dim3(256), 4 * 32 * 128, stream, p);
+    if (g_hooks.wgrad_tr) hipLaunchKernelGGL((wgrad_kernel<bf16, GEOM, true>), grid, dim3(256), 4 * 32 * 128, stream, p);
     else hipLaunchKernelGGL((wgrad_kernel<bf16, GEOM, false>), grid, dim3(256), 4 * 32 * 128, stream, p);
   } else if (dtype == PCRL_F32) {
     hipLaunchKernelGGL((wgrad_kernel<float, GEOM, false>), grid, dim3(256), 4 * 32 * 256, stream, p);
@@ -1186,7 +1180,7 @@ int run_wgrad(const void* u, const void* v, float* dw_ref, void* ws, size_t ws_b
 
 // ---- brick path of the 1-channel weight gradients ----
 bool scalar_brick_ok(int D, int H, int W, int C, int taps, int dtype) {
-  return dtype == PCRL_BF16 && g_wgrad_tr && taps == 27 && D % 4 == 0 && H % 8 == 0 && W % 8 == 0 && C % 8 == 0;
+  return dtype == PCRL_BF16 && g_hooks.wgrad_tr && taps == 27 && D % 4 == 0 && H % 8 == 0 && W % 8 == 0 && C % 8 == 0;
 }
 int scalar_brick_blocks(int64_t nbricks, int C) {
   const int ytiles = (C + 63) / 64;
@@ -1212,23 +1206,6 @@ int scalar_brick_launch(const void* act, const float* sfield, float* dw_ref, cha
   return launch_wgrad_reduce((const float*)part, dw_ref, blocks, 1, C, 32, 27, stream);
 }
 }  // namespace
-
-// Test hook (not part of the drop-in surface): select the bf16 fragment-fetch path.
-extern "C" void pcrl_debug_set_wgrad_tr(int on) { g_wgrad_tr = on; }
-
-// LDS-halo brick kernel (wgrad_brick.hip)
-bool pcrl_wgrad_brick_eligible(int N, int D, int H, int W, int Ci, int Co, int dtype);
-int pcrl_wgrad_brick_splits(int N, int D, int H, int W, int Ci, int Co);
-int pcrl_wgrad_brick_launch(const void* x, const void* dy, float* ws, int N, int D, int H, int W, int Ci, int Co, hipStream_t stream);
-int pcrl_wgrad_brick_slabs(int N, int D, int H, int W, int Ci, int Co);   // partial slabs the launch writes (<= pcrl_wgrad_brick_splits)
-void pcrl_wgrad_brick_set_xcd(int on, int order, int tiles);
-
-static std::atomic<int> g_wgrad_impl{0};  // 0 = auto (brick kernel where eligible), 1 = always the gather kernel, 2 = brick kernel on its 2-D grid (no XCD co-location)
-extern "C" void pcrl_debug_set_wgrad_impl(int impl) {
-  // experiments: 4 = co-located launch with the old walk order, 5 = 2-D grid with the new walk order, 6 = co-located launch with 64 x 64 tiles only
-  g_wgrad_impl = impl == 1 ? 1 : 0;
-  pcrl_wgrad_brick_set_xcd(impl == 0 || impl == 4 || impl == 6, impl == 0 || impl == 5 || impl == 6, impl != 6);
-}
 
 // ---- fused ConvTranspose3d(k2,s2) -> Conv3d(3x3x3): gradient of the COMPOSED weights (internal; the C ABI is in upconv_fused.hip) ----
 // dweff[co][ci][t], t = phase * 8 + coarse tap = sum over coarse voxels v of dy0[2v + p][co] * x[v + p - 1 + q][ci]
@@ -1265,7 +1242,7 @@ int pcrl_upc_wgrad_launch(const void* dy0, const void* x, float* dweff, void* ws
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_upc8_kernel<float, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 9 * 32 * 256);
   });
   if (dtype == PCRL_BF16) {
-    if (g_wgrad_tr) hipLaunchKernelGGL((wgrad_upc8_kernel<bf16, true>), grid, dim3(256), 2 * 9 * 32 * 128, stream, p);
+    if (g_hooks.wgrad_tr) hipLaunchKernelGGL((wgrad_upc8_kernel<bf16, true>), grid, dim3(256), 2 * 9 * 32 * 128, stream, p);
     else hipLaunchKernelGGL((wgrad_upc8_kernel<bf16, false>), grid, dim3(256), 2 * 9 * 32 * 128, stream, p);
   } else if (dtype == PCRL_F32) {
     hipLaunchKernelGGL((wgrad_upc8_kernel<float, false>), grid, dim3(256), 2 * 9 * 32 * 256, stream, p);
@@ -1277,12 +1254,6 @@ int pcrl_upc_wgrad_launch(const void* dy0, const void* x, float* dweff, void* ws
 }
 
 // the same gradient, dweff[co][ci][p * 8 + q], from the brick kernel (wgrad_brick.hip, composed up-conv mode) where it tiles the coarse grid
-bool pcrl_wgrad_brick_upc_eligible(int N, int D, int H, int W, int Ci, int Co, int dtype);
-int pcrl_wgrad_brick_upc_slabs(int N, int D, int H, int W, int Ci, int Co);
-int pcrl_wgrad_brick_upc_launch(const void* x, const void* dy0, float* ws, int N, int D, int H, int W, int Ci, int Co, hipStream_t stream);
-bool pcrl_upc_wgrad_uses_brick(int N, int D, int H, int W, int Ci, int Co, int dtype) {
-  return g_wgrad_impl == 0 && g_wgrad_tr && pcrl_wgrad_brick_upc_eligible(N, D, H, W, Ci, Co, dtype);
-}
 size_t pcrl_upc_wgrad3_ws_bytes(int N, int D, int H, int W, int Ci, int Co) {
   return (size_t)pcrl_wgrad_brick_upc_slabs(N, D, H, W, Ci, Co) * 27 * 8 * Co * Ci * sizeof(float);
 }
@@ -1291,7 +1262,7 @@ size_t pcrl_upc_wgrad3_ws_bytes(int N, int D, int H, int W, int Ci, int Co) {
 // into the compact layout of the gather form, out[co][ci][p * 8 + q] -- 8 / 27 of the slab bytes, no intermediate [8 * Co][Ci][27] array.
 // Block = one row i = p * Co + co and 64 columns ci: thread (q, lane) reads 128-byte runs, the tile is transposed through LDS so that the
 // eight q of a (co, ci) leave as one 32-byte run.
-__global__ void __launch_bounds__(256) wgrad_reduce_upc_kernel(const float* __restrict__ ws, float* __restrict__ out, int splits, int Co, int Ci,
+static __global__ void __launch_bounds__(256) wgrad_reduce_upc_kernel(const float* __restrict__ ws, float* __restrict__ out, int splits, int Co, int Ci,
                                                                bool accumulate) {
   __shared__ float tile[64][9];
   const int i = blockIdx.y, p = i / Co, co = i - p * Co, j0 = blockIdx.x * 64;
@@ -1328,6 +1299,24 @@ int pcrl_upc_wgrad3_launch(const void* dy0, const void* x, float* dweff, void* w
   return pcrl_check_launch("upconv wgrad (brick, reduce)");
 }
 
+// ---- one routing rule per weight-gradient operation: its launch switches on it.  The workspace queries know no dtype and no hook: they size for
+// the largest form a shape can take. ----
+enum Conv3WgradRoute { CONV3_WG_GATHER = 0, CONV3_WG_BRICK };   // LDS-halo brick kernel (wgrad_brick.hip) where eligible
+static Conv3WgradRoute conv3_wgrad_route(int N, int D, int H, int W, int Ci, int Co, int dtype) {
+  return g_hooks.wgrad_impl == 0 && pcrl_wgrad_brick_eligible(N, D, H, W, Ci, Co, dtype) ? CONV3_WG_BRICK : CONV3_WG_GATHER;
+}
+enum ConvtWgradRoute { CONVT_WG_GATHER = 0, CONVT_WG_ALLTAPS };   // wgrad_up2_alltaps_kernel: the eight taps of a tile in one block
+static ConvtWgradRoute convt_wgrad_route(int Ci, int Co, int dtype) {
+  return g_hooks.wgrad_impl == 0 && dtype == PCRL_BF16 && g_hooks.wgrad_tr && Ci % 64 == 0 && Co % 64 == 0 ? CONVT_WG_ALLTAPS : CONVT_WG_GATHER;
+}
+// the 1-channel convolutions (first layer: taps = 27; heads: 27 or 1): scalar brick kernel, weighted column sum (1x1x1), else im2col + plain GEMM
+enum ScalarWgradRoute { SCALAR_WG_PLAIN = 0, SCALAR_WG_BRICK, SCALAR_WG_POINTWISE };
+static ScalarWgradRoute scalar_wgrad_route(int D, int H, int W, int C, int taps, int dtype) {
+  if (g_hooks.wgrad_impl != 0) return SCALAR_WG_PLAIN;
+  if (scalar_brick_ok(D, H, W, C, taps, dtype)) return SCALAR_WG_BRICK;
+  return taps == 1 && C % (dtype == PCRL_BF16 ? 8 : 4) == 0 && C <= 512 ? SCALAR_WG_POINTWISE : SCALAR_WG_PLAIN;
+}
+
 extern "C" size_t pcrl_conv3d_k3_wgrad_ws_bytes(int N, int D, int H, int W, int Ci, int Co) {
   const SplitPlan sp = plan_splits((int64_t)N * D * H * W, Co, Ci, 27);
   size_t a = (size_t)sp.splits * 27 * Co * Ci * sizeof(float);
@@ -1342,7 +1331,7 @@ extern "C" int pcrl_conv3d_k3_wgrad(const void* x, const void* dy, float* dw_ref
                                     int N, int D, int H, int W, int Ci, int Co, int dtype, pcrl_stream_t stream) {
   PCRL_REQUIRE(x && dy && dw_ref, "conv3d_k3_wgrad: null pointer");
   PCRL_REQUIRE(Ci > 0 && Co > 0 && Ci % 32 == 0 && Co % 32 == 0, "conv3d_k3_wgrad: channels must be multiples of 32 (Ci=%d Co=%d)", Ci, Co);
-  if (g_wgrad_impl == 0 && pcrl_wgrad_brick_eligible(N, D, H, W, Ci, Co, dtype)) {
+  if (conv3_wgrad_route(N, D, H, W, Ci, Co, dtype) == CONV3_WG_BRICK) {
     const int splits = pcrl_wgrad_brick_slabs(N, D, H, W, Ci, Co);
     const size_t need = (size_t)splits * 27 * Co * Ci * sizeof(float);
     if (!ws || ws_bytes < need) return pcrl_fail(PCRL_EWORKSPACE, "conv3d_k3_wgrad: workspace %zu < %zu", ws_bytes, need);
@@ -1351,8 +1340,6 @@ extern "C" int pcrl_conv3d_k3_wgrad(const void* x, const void* dy, float* dw_ref
   }
   return run_wgrad<WG_CONV3>(dy, x, dw_ref, ws, ws_bytes, Dims{N, D, H, W}, Co, Ci, 27, dtype, as_stream(stream));
 }
-
-static bool up2_alltaps_ok(int Ci, int Co, int dtype) { return dtype == PCRL_BF16 && g_wgrad_tr && Ci % 64 == 0 && Co % 64 == 0; }
 
 extern "C" size_t pcrl_convt3d_k2s2_wgrad_ws_bytes(int N, int D, int H, int W, int Ci, int Co) {
   const int64_t M = (int64_t)N * D * H * W;
@@ -1369,7 +1356,7 @@ extern "C" int pcrl_convt3d_k2s2_wgrad(const void* x, const void* dy, float* dw_
                                        int N, int D, int H, int W, int Ci, int Co, int dtype, pcrl_stream_t stream) {
   PCRL_REQUIRE(x && dy && dw_ref, "convt3d_k2s2_wgrad: null pointer");
   PCRL_REQUIRE(Ci > 0 && Co > 0 && Ci % 32 == 0 && Co % 32 == 0, "convt3d_k2s2_wgrad: channels must be multiples of 32 (Ci=%d Co=%d)", Ci, Co);
-  if (g_wgrad_impl == 0 && up2_alltaps_ok(Ci, Co, dtype)) {
+  if (convt_wgrad_route(Ci, Co, dtype) == CONVT_WG_ALLTAPS) {
     const int64_t M = (int64_t)N * D * H * W;
     const SplitPlanUp2 sp = plan_up2(M, Ci, Co);
     const size_t need = (size_t)sp.splits * 8 * Co * Ci * sizeof(float);
@@ -1421,7 +1408,7 @@ extern "C" int pcrl_conv3d_k3_c1_wgrad(const float* x, const void* dy, float* dw
   PCRL_REQUIRE(Co > 0 && Co % 8 == 0, "conv3d_k3_c1_wgrad: Co must be a multiple of 8 (got %d)", Co);
   const int64_t M = (int64_t)N * D * H * W;
   const int esz = dtype == PCRL_BF16 ? 2 : 4;
-  if (g_wgrad_impl == 0 && scalar_brick_ok(D, H, W, Co, 27, dtype)) {
+  if (scalar_wgrad_route(D, H, W, Co, 27, dtype) == SCALAR_WG_BRICK) {
     if (!ws || ws_bytes < scalar_brick_ws_bytes(N, D, H, W, Co)) return pcrl_fail(PCRL_EWORKSPACE, "conv3d_k3_c1_wgrad: workspace too small");
     return scalar_brick_launch(dy, x, dw_ref, (char*)ws, N, D, H, W, Co, 0, as_stream(stream));
   }
@@ -1432,11 +1419,6 @@ extern "C" int pcrl_conv3d_k3_c1_wgrad(const float* x, const void* dy, float* dw
   if (int e = im2col_launch(x, col, g, M, 27, 0, dtype, as_stream(stream))) return e;
   return run_wgrad<WG_PLAIN>(dy, col, dw_ref, part, ws_bytes - (size_t)(part - col), g, Co, 32, 1, dtype, as_stream(stream), 27);
 }
-
-// weighted column sum (norm_pool.hip): the whole weight gradient of a 1x1x1 convolution to one channel
-size_t pcrl_weighted_colsum_ws_bytes(int64_t M, int C);
-int pcrl_weighted_colsum(const void* v, const float* rowscale, float* out, void* ws, size_t ws_bytes, int64_t M, int C, int dtype, hipStream_t stream);
-static bool to1_pointwise_ok(int C, int taps, int dtype) { return taps == 1 && C % (dtype == PCRL_BF16 ? 8 : 4) == 0 && C <= 512 && g_wgrad_impl == 0; }
 
 extern "C" size_t pcrl_conv3d_to1_wgrad_ws_bytes(int N, int D, int H, int W, int C, int taps) {
   size_t need = plain_ws_bytes((int64_t)N * D * H * W, C, 4);
@@ -1456,11 +1438,12 @@ extern "C" int pcrl_conv3d_to1_wgrad(const void* x, const float* dy, float* dw_r
   const Dims g{N, D, H, W};
   char* col = (char*)ws;
   double* red;
-  if (g_wgrad_impl == 0 && scalar_brick_ok(D, H, W, C, taps, dtype)) {
+  const ScalarWgradRoute route = scalar_wgrad_route(D, H, W, C, taps, dtype);
+  if (route == SCALAR_WG_BRICK) {
     if (!ws || ws_bytes < scalar_brick_ws_bytes(N, D, H, W, C)) return pcrl_fail(PCRL_EWORKSPACE, "conv3d_to1_wgrad: workspace too small");
     red = (double*)col;   // first 8 KiB of the workspace: partials of the bias gradient
     if (int e = scalar_brick_launch(x, dy, dw_ref, col, N, D, H, W, C, 1, as_stream(stream))) return e;
-  } else if (to1_pointwise_ok(C, taps, dtype)) {
+  } else if (route == SCALAR_WG_POINTWISE) {
     // 1x1x1: dw[c] = sum_m x[m][c] dy[m] -- one weighted column-sum pass over x (the im2col + split-K GEMM + reduce it replaces took
     // 0.44 ms per step for 64 numbers: 2048 partial slabs reduced by four blocks)
     if (!ws || ws_bytes < 8192 + pcrl_weighted_colsum_ws_bytes(M, C)) return pcrl_fail(PCRL_EWORKSPACE, "conv3d_to1_wgrad: workspace too small");
@@ -1510,17 +1493,18 @@ static SplitPlan plan_row3(int64_t M, int CoP, int CiP) {
   splits = (steps + per - 1) / per;
   return SplitPlan{(int)splits, per * 64};
 }
-static int conv2d_wgrad_ks(int dtype) { return (dtype == PCRL_BF16 && g_wgrad_tr) ? 128 : 32; }   // 128 (template KS) measured slower: the loads, not the barriers, set the pace
+static int conv2d_wgrad_ks(int dtype) { return (dtype == PCRL_BF16 && g_hooks.wgrad_tr) ? 128 : 32; }   // 128 (template KS) measured slower: the loads, not the barriers, set the pace
 
-// LDS-halo brick kernel with the image index as depth (wgrad_brick.hip, nkd = 1)
-bool pcrl_wgrad_brick2d_eligible(int N, int H, int W, int Ci, int Co, int dtype);
-int pcrl_wgrad_brick2d_splits(int N, int H, int W, int Ci, int Co);
-int pcrl_wgrad_brick2d_launch(const void* x, const void* dy, float* ws, int N, int H, int W, int Ci, int Co, int up, hipStream_t stream);
-
-// right-sized kernel for the 16/32-channel layers (wgrad2d_narrow.hip)
-bool pcrl_wgrad2d_narrow_eligible(int N, int H, int W, int CiP, int CoP, int dtype);
-int pcrl_wgrad2d_narrow_slabs(int N, int H, int W);
-int pcrl_wgrad2d_narrow_launch(const void* x, const void* dy, float* ws, int N, int H, int W, int CiP, int CoP, int up, hipStream_t stream);
+// right-sized kernel for the 16/32-channel layers (wgrad2d_narrow.hip) before the LDS-halo brick kernel with the image index as depth (wgrad_brick.hip,
+// nkd = 1), both for 3x3 / stride 1 / pad 1 at the output resolution; then one kernel row per block (wgrad2d_row3_kernel); else the gather kernel
+enum Conv2dWgradRoute { CONV2D_WG_GATHER = 0, CONV2D_WG_NARROW, CONV2D_WG_BRICK, CONV2D_WG_ROW3 };
+static Conv2dWgradRoute conv2d_wgrad_route(int N, int Hi, int Wi, int CiP, int Ho, int Wo, int CoP, int KH, int KW, int stride, int pad, int up, int dtype) {
+  if (g_hooks.wgrad_impl != 0 || !g_hooks.wgrad_tr) return CONV2D_WG_GATHER;
+  const bool same3 = KH == 3 && KW == 3 && stride == 1 && pad == 1 && (up ? (2 * Hi == Ho && 2 * Wi == Wo) : (Hi == Ho && Wi == Wo));
+  if (same3 && pcrl_wgrad2d_narrow_eligible(N, Ho, Wo, CiP, CoP, dtype)) return CONV2D_WG_NARROW;
+  if (same3 && pcrl_wgrad_brick2d_eligible(N, Ho, Wo, CiP, CoP, dtype)) return CONV2D_WG_BRICK;
+  return wgrad2d_row3_ok(CiP, CoP, KH, KW, dtype) ? CONV2D_WG_ROW3 : CONV2D_WG_GATHER;
+}
 
 extern "C" size_t pcrl_conv2d_wgrad_ws_bytes(int N, int Ho, int Wo, int CiP, int CoP, int KH, int KW) {
   // the largest of the variants (the dtype is not known here)
@@ -1550,16 +1534,15 @@ extern "C" int pcrl_conv2d_wgrad(const void* x, const void* dy, float* dw_ref, v
   PCRL_REQUIRE(KH >= 1 && KW >= 1 && KH * KW <= 49 && stride >= 1 && pad >= 0, "conv2d_wgrad: bad kernel geometry");
   PCRL_REQUIRE(dtype == PCRL_BF16 || dtype == PCRL_F32, "conv2d_wgrad: bad dtype %d", dtype);
   const int taps = KH * KW, Cv = taps * CiP;
-  if (g_wgrad_impl == 0 && g_wgrad_tr && KH == 3 && KW == 3 && stride == 1 && pad == 1 && (up ? (2 * Hi == Ho && 2 * Wi == Wo) : (Hi == Ho && Wi == Wo)) &&
-      pcrl_wgrad2d_narrow_eligible(N, Ho, Wo, CiP, CoP, dtype)) {
+  const Conv2dWgradRoute route = conv2d_wgrad_route(N, Hi, Wi, CiP, Ho, Wo, CoP, KH, KW, stride, pad, up, dtype);
+  if (route == CONV2D_WG_NARROW) {
     const int slabs = pcrl_wgrad2d_narrow_slabs(N, Ho, Wo);
     const size_t need = (size_t)slabs * 9 * CoP * CiP * sizeof(float);
     if (!ws || ws_bytes < need) return pcrl_fail(PCRL_EWORKSPACE, "conv2d_wgrad: workspace %zu < %zu", ws_bytes, need);
     if (int e = pcrl_wgrad2d_narrow_launch(x, dy, (float*)ws, N, Ho, Wo, CiP, CoP, up, as_stream(stream))) return e;
     return launch_wgrad2d_reduce((const float*)ws, dw_ref, slabs, 9, CoP, CiP, Ci_out, as_stream(stream));
   }
-  if (g_wgrad_impl == 0 && g_wgrad_tr && KH == 3 && KW == 3 && stride == 1 && pad == 1 && (up ? (2 * Hi == Ho && 2 * Wi == Wo) : (Hi == Ho && Wi == Wo)) &&
-      pcrl_wgrad_brick2d_eligible(N, Ho, Wo, CiP, CoP, dtype)) {
+  if (route == CONV2D_WG_BRICK) {
     const int splits = pcrl_wgrad_brick2d_splits(N, Ho, Wo, CiP, CoP);
     const size_t need = (size_t)splits * 9 * CoP * CiP * sizeof(float);
     if (!ws || ws_bytes < need) return pcrl_fail(PCRL_EWORKSPACE, "conv2d_wgrad: workspace %zu < %zu", ws_bytes, need);
@@ -1568,7 +1551,7 @@ extern "C" int pcrl_conv2d_wgrad(const void* x, const void* dy, float* dw_ref, v
   }
   const Dims g{N, 1, Ho, Wo};
   const int64_t M = (int64_t)N * Ho * Wo;
-  if (g_wgrad_impl == 0 && g_wgrad_tr && wgrad2d_row3_ok(CiP, CoP, KH, KW, dtype)) {
+  if (route == CONV2D_WG_ROW3) {
     const SplitPlan sp = plan_row3(M, CoP, CiP);
     const size_t need = (size_t)sp.splits * CoP * Cv * sizeof(float);
     if (ws_bytes < need || !ws) return pcrl_fail(PCRL_EWORKSPACE, "conv2d_wgrad: workspace %zu < %zu", ws_bytes, need);
@@ -1588,7 +1571,7 @@ extern "C" int pcrl_conv2d_wgrad(const void* x, const void* dy, float* dw_ref, v
   dim3 grid((unsigned)(((CoP + 63) / 64) * ((Cv + 63) / 64)), 1u, (unsigned)sp.splits);
   hipStream_t st = as_stream(stream);
   if (dtype == PCRL_BF16) {
-    if (g_wgrad_tr) hipLaunchKernelGGL((wgrad_kernel<bf16, WG_CONV2D, true, 128>), grid, dim3(256), 4 * 128 * 128, st, p);
+    if (g_hooks.wgrad_tr) hipLaunchKernelGGL((wgrad_kernel<bf16, WG_CONV2D, true, 128>), grid, dim3(256), 4 * 128 * 128, st, p);
     else hipLaunchKernelGGL((wgrad_kernel<bf16, WG_CONV2D, false>), grid, dim3(256), 4 * 32 * 128, st, p);
   } else {
     hipLaunchKernelGGL((wgrad_kernel<float, WG_CONV2D, false>), grid, dim3(256), 4 * 32 * 256, st, p);

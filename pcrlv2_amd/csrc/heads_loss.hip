@@ -903,7 +903,7 @@ struct CatParams {
   int64_t vec_end[8];   // exclusive end of piece k in 16-byte vectors of dst
   int n;
 };
-__global__ void __launch_bounds__(256) concat_kernel(const CatParams c, uint4* __restrict__ dst) {
+static __global__ void __launch_bounds__(256) concat_kernel(const CatParams c, uint4* __restrict__ dst) {
   const int64_t total = c.vec_end[c.n - 1];
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     int k = 0;
@@ -939,7 +939,7 @@ constexpr int GS_MAX = 480;
 struct GradSrc {
   const float* s[GS_MAX];
 };
-__global__ void __launch_bounds__(256) grad_sum_kernel(float* __restrict__ dst, const int64_t* __restrict__ offsets, const int64_t* __restrict__ numels,
+static __global__ void __launch_bounds__(256) grad_sum_kernel(float* __restrict__ dst, const int64_t* __restrict__ offsets, const int64_t* __restrict__ numels,
                                                        const GradSrc src, int t0, int cnt, int nsrc) {
   const int64_t base = offsets[t0], total = offsets[t0 + cnt] - base;
   const int64_t ngroups = (total + 3) >> 2;
@@ -1004,7 +1004,7 @@ extern "C" int pcrl_grad_sum(float* dst, const int64_t* offsets, const int64_t* 
 }
 
 // total = l1 + l2 + beta * l4 + l5 and scaled = beta * l4 in one launch (train_3d.py:136-138): out[0] = total, out[1] = scaled
-__global__ void loss_total_kernel(const float* __restrict__ l1, const float* __restrict__ l2, const float* __restrict__ l4, const float* __restrict__ l5,
+static __global__ void loss_total_kernel(const float* __restrict__ l1, const float* __restrict__ l2, const float* __restrict__ l4, const float* __restrict__ l5,
                                   float beta, float* __restrict__ out) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     const float s = beta * l4[0];
@@ -1019,7 +1019,7 @@ extern "C" int pcrl_loss_total(const float* l1, const float* l2, const float* l4
 }
 
 // backward of pcrl_loss_total: out = (g, beta * g, g, g) -- the gradients of loss1, l4 and of the two cosine groups (global, local)
-__global__ void loss_total_bwd_kernel(const float* __restrict__ g, float beta, float* __restrict__ out) {
+static __global__ void loss_total_bwd_kernel(const float* __restrict__ g, float beta, float* __restrict__ out) {
   if (threadIdx.x < 4) out[threadIdx.x] = threadIdx.x == 1 ? beta * g[0] : g[0];
 }
 extern "C" int pcrl_loss_total_bwd(const float* g, float beta, float* out, pcrl_stream_t stream) {
@@ -1053,7 +1053,7 @@ extern "C" int pcrl_sgd_step_guarded(float* p, const float* g, float* buf, const
 }
 
 // out[0] = (loss > threshold) ? 1 : 0, NaN counts as diverged exactly when the reference's `loss > 1000` would (it would not: NaN > x is false).
-__global__ void guard_flag_kernel(const float* __restrict__ loss, float threshold, float* __restrict__ out) {
+static __global__ void guard_flag_kernel(const float* __restrict__ loss, float threshold, float* __restrict__ out) {
   if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = (loss[0] > threshold) ? 1.f : 0.f;
 }
 

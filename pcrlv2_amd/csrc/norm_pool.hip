@@ -5,7 +5,7 @@
 // Replaces aten::native_batch_norm(+_backward), relu_/threshold_backward, sigmoid(+_backward)
 // (models/pcrlv2_model_3d.py:12,21,27,33), max_pool3d_with_indices(+backward) (:100,115-117) and
 // adaptive_avg_pool3d(+backward) (:67).
-#include "common.h"
+#include "internal.h"
 
 namespace {
 

@@ -22,34 +22,7 @@
 // The three data-sized passes (forward, dx, dWeff) run in the gather implicit-GEMM kernels (conv_igemm.hip GEOM_UPC_*, conv_wgrad.hip
 // WG_UPC); the weight-sized algebra runs as MFMA GEMMs with float32 plane-major results (pcrl_gemm_planes_launch) between small
 // re-layout kernels in this file.  Parameters, their gradients and the state_dict stay those of the two reference layers.
-#include "common.h"
-
-// conv_igemm.hip / conv_wgrad.hip
-int pcrl_upc_fwd_launch(const void* x, const void* wf, const float* bias_tab, void* y0, float* stats, int N, int D, int H, int W, int Ci, int Co,
-                        int dtype, hipStream_t stream);
-int pcrl_upc_dgrad_launch(const void* dy0, const void* wd, void* dx, void* ws, int64_t ws_bytes, int N, int D, int H, int W, int Ci, int Co, int dtype,
-                          hipStream_t stream);
-int64_t pcrl_upc_dgrad_ws_bytes(int N, int D, int H, int W, int Ci, int Co);   // split-K workspace of the gather form (0: none)
-bool pcrl_upc_fwd_uses_brick(int N, int D, int H, int W, int Ci, int Co, int dtype);   // conv_igemm.hip: a brick kernel takes this shape
-int pcrl_upc_fwd_impl(int N, int D, int H, int W, int Ci, int Co, int dtype);           // 0 gather, 1 wide brick (conv_brick16.hip), 2 4 x 8 x 8 brick (conv_brick.hip)
-int pcrl_upc_dgrad_impl(int N, int D, int H, int W, int Ci, int Co, int dtype);
-int64_t pcrl_brick16_conv_rows(int N, int D, int H, int W);
-int64_t pcrl_brick_conv_rows(int N, int D, int H, int W);
-int pcrl_brick8_upc_fwd_launch(const void* x, const void* w3, const float* bias_tab, void* y0, float* stats, int N, int D, int H, int W, int Ci, int Co,
-                               hipStream_t stream);
-int pcrl_brick8_upc_dgrad_launch(const void* dy0, const void* wd3, void* dx, int N, int D, int H, int W, int Ci, int Co, hipStream_t stream);
-int pcrl_brick16_upc_fwd_launch(const void* x, const void* w3, const float* bias_tab, void* y0, float* stats, int N, int D, int H, int W, int Ci, int Co,
-                                hipStream_t stream);
-bool pcrl_upc_dgrad_uses_brick(int N, int D, int H, int W, int Ci, int Co, int dtype);
-int pcrl_brick16_upc_dgrad_launch(const void* dy0, const void* wd3, void* dx, int N, int D, int H, int W, int Ci, int Co, hipStream_t stream);
-int pcrl_gemm_planes_launch(const void* a, const void* b, float* z, int64_t M, int K, int Nc, int dtype, hipStream_t stream);
-size_t pcrl_upc_wgrad_ws_bytes(int N, int D, int H, int W, int Ci, int Co);
-int pcrl_upc_wgrad_launch(const void* dy0, const void* x, float* dweff, void* ws, size_t ws_bytes, int N, int D, int H, int W, int Ci, int Co,
-                          int dtype, hipStream_t stream, bool accumulate);
-bool pcrl_upc_wgrad_uses_brick(int N, int D, int H, int W, int Ci, int Co, int dtype);
-size_t pcrl_upc_wgrad3_ws_bytes(int N, int D, int H, int W, int Ci, int Co);
-int pcrl_upc_wgrad3_launch(const void* dy0, const void* x, float* dweff, void* ws, size_t ws_bytes, int N, int D, int H, int W, int Ci, int Co,
-                           hipStream_t stream, bool accumulate);
+#include "internal.h"
 
 namespace {
 
@@ -510,8 +483,7 @@ extern "C" int pcrl_upconv_compose(const float* w_up, const float* b_up, const f
   const unsigned gp = blocks_for((int64_t)64 * Ci * Co);
   if (w3f) (void)hipMemsetAsync(w3f, 0, (size_t)216 * Ci * Co * esz(dtype), st);   // 19 of a phase's 27 taps stay zero
   if (wd3) (void)hipMemsetAsync(wd3, 0, (size_t)216 * Ci * Co * esz(dtype), st);   // a parity holds 8 of the 27 taps
-  static const bool tiled_on = [] { const char* e = getenv("PCRL_UPC_PACK_TILED"); return !(e && e[0] == '0'); }();   // A/B switch (bit-identical outputs)
-  if (tiled_on && Ci % 32 == 0 && Co % 32 == 0 && Co / 32 <= 65535) {
+  if (pcrl_env().upc_pack_tiled && Ci % 32 == 0 && Co % 32 == 0 && Co / 32 <= 65535) {
     const dim3 gt((unsigned)(Ci / 32), 64, (unsigned)(Co / 32));
     if (dtype == PCRL_BF16) hipLaunchKernelGGL(upc_pack_tiled_kernel<bf16>, gt, dim3(256), 0, st, (const float*)P, (bf16*)wf, (bf16*)wd, (bf16*)w3f, (bf16*)wd3, Ci, Co);
     else hipLaunchKernelGGL(upc_pack_tiled_kernel<float>, gt, dim3(256), 0, st, (const float*)P, (float*)wf, (float*)wd, (float*)w3f, (float*)wd3, Ci, Co);
@@ -523,36 +495,51 @@ extern "C" int pcrl_upconv_compose(const float* w_up, const float* b_up, const f
 }
 
 // ---- forward / data gradient ----
+// The kernel family of each pass -- the ONE routing rule behind its queries and its launch: wide brick (conv_brick16_upc.hip) before 4 x 8 x 8 brick
+// (conv_brick.hip) before the gather kernel (conv_igemm.hip).
+enum UpcRoute { UPC_GATHER = 0, UPC_BRICK16, UPC_BRICK8 };
+static UpcRoute upc_fwd_route(int N, int D, int H, int W, int Ci, int Co, int dtype) {
+  if (g_hooks.conv_impl != 0) return UPC_GATHER;
+  if (pcrl_brick16_upc_fwd_eligible(N, D, H, W, Ci, Co, dtype)) return UPC_BRICK16;
+  return pcrl_brick8_upc_fwd_eligible(N, D, H, W, Ci, Co, dtype) ? UPC_BRICK8 : UPC_GATHER;
+}
+static UpcRoute upc_dgrad_route(int N, int D, int H, int W, int Ci, int Co, int dtype) {
+  if (g_hooks.conv_impl != 0) return UPC_GATHER;
+  if (pcrl_brick16_upc_dgrad_eligible(N, D, H, W, Ci, Co, dtype)) return UPC_BRICK16;
+  return pcrl_brick8_upc_dgrad_eligible(N, D, H, W, Ci, Co, dtype) ? UPC_BRICK8 : UPC_GATHER;
+}
 extern "C" int64_t pcrl_upconv_fwd_uses_brick(int N, int D, int H, int W, int Ci, int Co, int dtype) {
-  return pcrl_upc_fwd_uses_brick(N, D, H, W, Ci, Co, dtype) ? 1 : 0;
+  return upc_fwd_route(N, D, H, W, Ci, Co, dtype) != UPC_GATHER;
 }
 extern "C" int64_t pcrl_upconv_stats_rows(int N, int D, int H, int W, int Ci, int Co, int dtype) {
-  const int impl = pcrl_upc_fwd_impl(N, D, H, W, Ci, Co, dtype);
-  if (impl == 1) return 8 * pcrl_brick16_conv_rows(N, D, H, W);
-  if (impl == 2) return 8 * pcrl_brick_conv_rows(N, D, H, W);
+  switch (upc_fwd_route(N, D, H, W, Ci, Co, dtype)) {
+    case UPC_BRICK16: return 8 * pcrl_brick16_conv_rows(N, D, H, W);
+    case UPC_BRICK8: return 8 * pcrl_brick_conv_rows(N, D, H, W);
+    case UPC_GATHER: break;
+  }
   return 8 * (((int64_t)N * D * H * W + PCRL_CONV_BM - 1) / PCRL_CONV_BM);
 }
 extern "C" int pcrl_upconv_fwd(const void* x, const void* wf, const void* w3f, const float* bias_tab, void* y0, float* stats_partial, int N, int D, int H,
                                int W, int Ci, int Co, int dtype, pcrl_stream_t stream) {
   if (int e = check_upc("upconv_fwd", N, D, H, W, Ci, 32, Co, dtype)) return e;
   PCRL_REQUIRE(x && wf && bias_tab && y0, "upconv_fwd: null pointer");
-  if (const int impl = pcrl_upc_fwd_impl(N, D, H, W, Ci, Co, dtype)) {
+  if (const UpcRoute route = upc_fwd_route(N, D, H, W, Ci, Co, dtype)) {
     PCRL_REQUIRE(w3f, "upconv_fwd: this shape runs on a brick kernel and needs the 3x3x3 form of the composed weights (w3f)");
-    if (impl == 2) return pcrl_brick8_upc_fwd_launch(x, w3f, bias_tab, y0, stats_partial, N, D, H, W, Ci, Co, as_stream(stream));
+    if (route == UPC_BRICK8) return pcrl_brick8_upc_fwd_launch(x, w3f, bias_tab, y0, stats_partial, N, D, H, W, Ci, Co, as_stream(stream));
     return pcrl_brick16_upc_fwd_launch(x, w3f, bias_tab, y0, stats_partial, N, D, H, W, Ci, Co, as_stream(stream));
   }
   return pcrl_upc_fwd_launch(x, wf, bias_tab, y0, stats_partial, N, D, H, W, Ci, Co, dtype, as_stream(stream));
 }
 extern "C" int64_t pcrl_upconv_dgrad_uses_brick(int N, int D, int H, int W, int Ci, int Co, int dtype) {
-  return pcrl_upc_dgrad_uses_brick(N, D, H, W, Ci, Co, dtype) ? 1 : 0;
+  return upc_dgrad_route(N, D, H, W, Ci, Co, dtype) != UPC_GATHER;
 }
 static int upconv_dgrad_impl(const void* dy0, const void* wd, const void* wd3, void* dx, void* ws, int64_t ws_bytes, int N, int D, int H, int W, int Ci,
                              int Co, int dtype, pcrl_stream_t stream) {
   if (int e = check_upc("upconv_dgrad", N, D, H, W, Ci, 32, Co, dtype)) return e;
   PCRL_REQUIRE(dy0 && wd && dx, "upconv_dgrad: null pointer");
-  if (const int impl = pcrl_upc_dgrad_impl(N, D, H, W, Ci, Co, dtype)) {
+  if (const UpcRoute route = upc_dgrad_route(N, D, H, W, Ci, Co, dtype)) {
     PCRL_REQUIRE(wd3, "upconv_dgrad: this shape runs on a brick kernel and needs the 3x3x3 form of the composed weights (wd3)");
-    if (impl == 2) return pcrl_brick8_upc_dgrad_launch(dy0, wd3, dx, N, D, H, W, Ci, Co, as_stream(stream));
+    if (route == UPC_BRICK8) return pcrl_brick8_upc_dgrad_launch(dy0, wd3, dx, N, D, H, W, Ci, Co, as_stream(stream));
     return pcrl_brick16_upc_dgrad_launch(dy0, wd3, dx, N, D, H, W, Ci, Co, as_stream(stream));
   }
   return pcrl_upc_dgrad_launch(dy0, wd, dx, ws, ws_bytes, N, D, H, W, Ci, Co, dtype, as_stream(stream));
@@ -565,7 +552,7 @@ extern "C" int pcrl_upconv_dgrad(const void* dy0, const void* wd, const void* wd
 // sums and a finish pass, like pcrl_conv3d_k3_fwd_ws.  pcrl_upconv_dgrad_ws_bytes() == 0: no workspace needed (ws may be null).
 extern "C" int64_t pcrl_upconv_dgrad_ws_bytes(int N, int D, int H, int W, int Ci, int Co, int dtype) {
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || Ci % 32 || Co % 32) return 0;
-  if (pcrl_upc_dgrad_uses_brick(N, D, H, W, Ci, Co, dtype)) return 0;
+  if (upc_dgrad_route(N, D, H, W, Ci, Co, dtype) != UPC_GATHER) return 0;
   return pcrl_upc_dgrad_ws_bytes(N, D, H, W, Ci, Co);
 }
 extern "C" int pcrl_upconv_dgrad_ws(const void* dy0, const void* wd, const void* wd3, void* dx, void* ws, int64_t ws_bytes, int N, int D, int H, int W,
@@ -594,12 +581,15 @@ FinLayout fin_layout(int Ci, int Cm, int Co, int dtype) {
   return L;
 }
 }  // namespace
-extern "C" int64_t pcrl_upconv_wgrad_uses_brick(int N, int D, int H, int W, int Ci, int Co, int dtype) {
-  return pcrl_upc_wgrad_uses_brick(N, D, H, W, Ci, Co, dtype) ? 1 : 0;
+// The gradient of the composed weights comes from the brick weight-gradient kernel (wgrad_brick.hip, composed up-conv mode) where it tiles the coarse grid
+enum UpcWgradRoute { UPC_WG_GATHER = 0, UPC_WG_BRICK = 1 };
+static UpcWgradRoute upc_wgrad_route(int N, int D, int H, int W, int Ci, int Co, int dtype) {
+  return g_hooks.wgrad_impl == 0 && g_hooks.wgrad_tr && pcrl_wgrad_brick_upc_eligible(N, D, H, W, Ci, Co, dtype) ? UPC_WG_BRICK : UPC_WG_GATHER;
 }
+extern "C" int64_t pcrl_upconv_wgrad_uses_brick(int N, int D, int H, int W, int Ci, int Co, int dtype) { return upc_wgrad_route(N, D, H, W, Ci, Co, dtype); }
 static size_t acc_wg_bytes(int N, int D, int H, int W, int Ci, int Co, int dtype) {
   const size_t a = pcrl_upc_wgrad_ws_bytes(N, D, H, W, Ci, Co);
-  if (!pcrl_upc_wgrad_uses_brick(N, D, H, W, Ci, Co, dtype)) return a;
+  if (upc_wgrad_route(N, D, H, W, Ci, Co, dtype) == UPC_WG_GATHER) return a;
   const size_t b = pcrl_upc_wgrad3_ws_bytes(N, D, H, W, Ci, Co);
   return a > b ? a : b;
 }
@@ -619,7 +609,7 @@ extern "C" int pcrl_upconv_wgrad_accum(const void* x, const void* dy0, float* dw
   hipStream_t st = as_stream(stream);
   char* w = (char*)ws;
   const size_t wgb = al(acc_wg_bytes(N, D, H, W, Ci, Co, dtype));
-  if (pcrl_upc_wgrad_uses_brick(N, D, H, W, Ci, Co, dtype)) {
+  if (upc_wgrad_route(N, D, H, W, Ci, Co, dtype) == UPC_WG_BRICK) {
     if (int e = pcrl_upc_wgrad3_launch(dy0, x, dweff_acc, w, wgb, N, D, H, W, Ci, Co, st, first == 0)) return e;
   } else {
     if (int e = pcrl_upc_wgrad_launch(dy0, x, dweff_acc, w, wgb, N, D, H, W, Ci, Co, dtype, st, first == 0)) return e;

@@ -10,7 +10,7 @@
 // CU/16 A fragments (dy, transpose reads) x 9 taps x CV/16 B fragments (x at the tap's shifted position, transpose reads).
 // Accumulators (CU/16 x 9 x CV/16 fragments) stay in registers over the block's whole patch range; every WAVE writes its own
 // partials in the block (fixed order) and the block writes one slab, summed in fixed order by wgrad2d_reduce_kernel (conv_wgrad.hip).
-#include "common.h"
+#include "internal.h"
 
 namespace {
 

@@ -22,8 +22,7 @@
 //   128 x 64  two dy images; group g owns co half g, every wave walks all four K chunks (Co % 128 == 0)                  7.1
 //   64 x 128  two x images; group g owns ci half g (Ci % 128 == 0)                                                       8.3
 //   64 x 32   Ci == 32: a wave owns 32 co x 16 ci (two A fragments) -- with 64 x 64 tiles half of the waves multiplied zero columns
-#include "common.h"
-#include <atomic>
+#include "internal.h"
 #include <mutex>
 
 // x-fragment prefetch distance in steps.  Two waves per SIMD hide the LDS latency between them: 1 is enough (2 and 3 measured equal).
@@ -944,13 +943,10 @@ struct BrickSplit {
   int cfg;                                              // tile shape: 0 = 64 x 64, 1 = 128 x 64, 2 = 64 x 128, 3 = 64 x 32
 };
 constexpr int TCO_OF[4] = {64, 128, 64, 64}, TCI_OF[4] = {64, 64, 128, 32};
-std::atomic<int> g_wb_xcd{1};    // 0: the 2-D grid (a (tile, kd) block range per blockIdx.y)
-std::atomic<int> g_wb_order{1};
-std::atomic<int> g_wb_tiles{1};  // 0: 64 x 64 tiles only
 
 // tile shape by staged bytes per MFMA (256 / TCI + 400 / TCO, see the head of the file)
 int pick_cfg(int Cu, int Cv) {
-  if (!g_wb_tiles) return 0;
+  if (!g_hooks.wb_tiles) return 0;
   if (Cv == 32) return 3;
   if (Cu % 128 == 0) return 1;
   if (Cv % 128 == 0) return 2;
@@ -1004,7 +1000,7 @@ BrickSplit plan_xcd(int nbricks, int Cu, int Cv, int cfg) {
 }
 
 BrickSplit plan3(int nbricks, int Cu, int Cv) {
-  if (!g_wb_xcd) return plan(nbricks, Cu, Cv);
+  if (!g_hooks.wb_xcd) return plan(nbricks, Cu, Cv);
   const int cfg = pick_cfg(Cu, Cv);
   const BrickSplit a = plan_xcd(nbricks, Cu, Cv, cfg);
   if (cfg == 0 || cfg == 3) return a;
@@ -1040,7 +1036,7 @@ bool pcrl_wgrad_brick_eligible(int N, int D, int H, int W, int Ci, int Co, int d
 // the one-plane kernel is no longer bound by its staging (both forms sit at ~0.8 transpose reads per MFMA), and on small volumes the
 // larger tile count of the one-plane form fills the chip better -- so: Ci = 32 always, Ci = 64 from 8 192 bricks on.
 static bool wb27_on(int Ci, int Co, int nbricks) {
-  return g_wb_tiles && Co == 64 && (Ci == 32 || (Ci == 64 && nbricks >= 8192));
+  return g_hooks.wb_tiles && Co == 64 && (Ci == 32 || (Ci == 64 && nbricks >= 8192));
 }
 static void wb27_plan(int nbricks, int Ci, int Co, int& splits, int& per) {
   const int ntile = (Co / 64) * (Ci / 32);
@@ -1078,14 +1074,13 @@ int pcrl_wgrad_brick_slabs(int N, int D, int H, int W, int Ci, int Co) {
   }
   return plan3(nb, Co, Ci).splits;
 }
-void pcrl_wgrad_brick_set_xcd(int on, int order, int tiles) { g_wb_xcd = on; g_wb_order = order; g_wb_tiles = tiles; }
 int pcrl_wgrad_brick_launch(const void* x, const void* dy, float* ws, int N, int D, int H, int W, int Ci, int Co,
                             hipStream_t stream) {
   const int nbricks = (int)((int64_t)N * D * H * W / BV);
   if (wb27_on(Ci, Co, nbricks)) {
     int splits, per;
     wb27_plan(nbricks, Ci, Co, splits, per);
-    WBrick27Params q{(const bf16*)dy, (const bf16*)x, ws, N, D, H, W, Co, Ci, nbricks, per, splits, H * W, W, 1, 9, 3, 1, g_wb_order};
+    WBrick27Params q{(const bf16*)dy, (const bf16*)x, ws, N, D, H, W, Co, Ci, nbricks, per, splits, H * W, W, 1, 9, 3, 1, g_hooks.wb_order};
     if (!wb_natural(D, H, W)) {   // memory (D, H, W) -> brick axes (W, D, H)
       q.D = W; q.H = D; q.W = H;
       q.sd = 1; q.sh = H * W; q.sw = W;
@@ -1101,7 +1096,7 @@ int pcrl_wgrad_brick_launch(const void* x, const void* dy, float* ws, int N, int
   }
   const BrickSplit sp = plan3(nbricks, Co, Ci);
   WBrickParams p{(const bf16*)dy, (const bf16*)x, ws, N, D, H, W, Co, Ci, nbricks, sp.per_split, 0, 3, H * W, W, 1, 9, 3, 1,
-                 sp.xcd_map, g_wb_order, sp.G, sp.Q, sp.gpc, sp.ngroups, sp.ntg, sp.pair};
+                 sp.xcd_map, g_hooks.wb_order, sp.G, sp.Q, sp.gpc, sp.ngroups, sp.ntg, sp.pair};
   if (!wb_natural(D, H, W)) {   // memory (D, H, W) -> brick axes (W, D, H); tap (kd', kh', kw') = (kw, kd, kh) -> index kh' * 9 + kw' * 3 + kd'
     p.D = W; p.H = D; p.W = H;
     p.sd = 1; p.sh = H * W; p.sw = W;
@@ -1146,7 +1141,7 @@ int pcrl_wgrad_brick_upc_launch(const void* x, const void* dy0, float* ws, int N
   int splits, per;
   upc2_plan(nbricks, Ci, Co, splits, per);
   WBrick2Params p{(const bf16*)dy0, (const bf16*)x, ws, N, D, H, W, Co, Ci, nbricks, per, splits, H * W, W, 1, 9, 3, 1, 8 * H * W, 4 * W, 2,
-                  (int64_t)8 * D * H * W, {0, 0, 0, 0, 0, 0, 0, 0}, 2, 1, 0, g_wb_order};
+                  (int64_t)8 * D * H * W, {0, 0, 0, 0, 0, 0, 0, 0}, 2, 1, 0, g_hooks.wb_order};
   for (int ph = 0; ph < 8; ++ph) p.phoff[ph] = (((ph >> 2) & 1) * (2 * H) + ((ph >> 1) & 1)) * (2 * W) + (ph & 1);
   if (!wb_natural(D, H, W)) {   // memory (D, H, W) -> brick axes (W, D, H)
     p.D = W; p.H = D; p.W = H;

@@ -30,8 +30,6 @@ ap.add_argument("--d", type=int, default=3, choices=[2, 3], help="2: the C5 per-
 a = ap.parse_args()
 dev = torch.device("cuda")
 L = _lib.lib()
-L.cdll.pcrl_debug_set_reduce_repeat.argtypes = [__import__("ctypes").c_int]
-L.cdll.pcrl_debug_set_reduce_repeat.restype = None
 
 
 def small(name, args):   # convolution launches on volumes of <= 64 voxels
@@ -139,7 +137,7 @@ def block(which):
     if which == "no_bnred":           # not a doubling: the separate first BatchNorm-backward pass instead of the data gradient's fused one (config.DGRAD_BNRED)
         config.DGRAD_BNRED = False
     elif which == "wgrad_reduce":
-        L.cdll.pcrl_debug_set_reduce_repeat(2)
+        L.debug_set_reduce_repeat(2)
     elif which is not None:
         active[0] = SETS[which]
     random.setstate(st0)
@@ -154,7 +152,7 @@ def block(which):
     torch.cuda.synchronize()
     active[0] = None
     config.DGRAD_BNRED = True
-    L.cdll.pcrl_debug_set_reduce_repeat(1)
+    L.debug_set_reduce_repeat(1)
     return e0.elapsed_time(e1) / a.steps
 
 
