@@ -305,6 +305,22 @@ int pcrl_val_metrics(const float* out1, const float* mask0, const float* mask1, 
                      const float* pro1_2, const float* pre1_2, const float* pro2_2, const float* pre2_2, const float* proL_2, const float* preL_2,
                      double* acc, void* ws, size_t ws_bytes, int B, int64_t S, int nlocal, int C0, int C1, int C2, float eps, pcrl_stream_t stream);
 
+/* Validation metrics of one 2D batch (the loss terms of train_2d.py:139-168 -- aten::mse_loss at :165,167, cos_loss :111-117 -- at EVERY scale index
+ * k = 0..4 instead of the drawn one, with pcrlv2_model.py:190's aten::upsample_bilinear2d inside the reduction), added to 17 device doubles:
+ *   acc[0] += B MSE(out1, gt);  acc[1 + k] += B MSE(bilinear_up(mask_k, 2^(4 - k)), gt)   (the upsampled map is never stored)
+ *   acc[6 + k] += B * -(mean cos(pre1_k, pro2_k) + mean cos(pre2_k, pro1_k)) / 2                                    (train_2d.py:111-117 at index k)
+ *   acc[11 + k] += B * mean over local views i and global views v of -(mean cos(pre_v, proL_i) + mean cos(preL_i, pro_v)) / 2     (train_2d.py:148-163)
+ *   acc[16] += B.
+ * out1: float32 NHWC [B][H][W][3]; masks: HOST array of 5 device pointers, mask_k float32 NHWC [B][H >> (4-k)][W >> (4-k)][3] at its own resolution
+ * (index rule of pcrl_upsample2d_bilinear_fwd, align_corners=False); gt: float32 NCHW [B][3][H][W] as the loader delivers it (as pcrl_mse2d_fwd reads
+ * it); feats: HOST array of 30 device pointers, scale-major: pro1, pre1, pro2, pre2 [B][C[k]], proL, preL [nlocal * B][C[k]] (local view i in rows
+ * i * B ..); C: HOST array of the 5 channel counts.  H, W multiples of 16.  nlocal, eps, row layout: the rules of pcrl_val_metrics.  Deterministic: two
+ * stages in fixed order, float64 arithmetic on the float32 inputs (dyadic interpolation weights: exact products), three launches, no atomics, no host
+ * synchronisation.  ws: pcrl_val2d_metrics_ws_bytes(B, H, W, nlocal). */
+size_t pcrl_val2d_metrics_ws_bytes(int B, int H, int W, int nlocal);
+int pcrl_val2d_metrics(const float* out1, const float* const* masks, const float* gt, const float* const* feats, const int* C, double* acc,
+                       void* ws, size_t ws_bytes, int B, int H, int W, int nlocal, float eps, pcrl_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * OPTIONAL EXTRA, not part of the reference: NT-Xent (SimCLR) contrastive loss over z = [z1; z2], R = 2N
  * rows (row i's positive is row (i + N) mod R), temperature tau:
@@ -369,6 +385,20 @@ int pcrl_conv2d_fwd(const void* x, const void* wp, const float* bias, void* y, f
  * nothing reads (14 of the 15 heads of a step, pcrlv2_model.py:103-106 / train_2d.py:143-168) runs for its BatchNorm's running statistics alone; its
  * output (537 MB at 512 x 512 x 16 channels, b = 64) is not written.  The statistics are taken from the float32 accumulators either way. */
 int64_t pcrl_conv2d_fwd_stats_only_ok(int N, int Hi, int Wi, int CiP, int Co, int KH, int KW, int stride, int pad, int up, int out_f32, int dtype);
+/* Inference forward of Conv2d -> BatchNorm2d (-> + identity) -> ReLU in .eval() (torchvision BasicBlock / smp Conv2dReLU as the reference's
+ * models/pcrlv2_model.py:68-128,197-209 runs them: aten::convolution -> aten::native_batch_norm on the running statistics -> aten::add -> aten::relu)
+ * as ONE pass:  a[m][co] = max(scale[co] * (acc + bias[co]) + shift[co] + (residual ? residual[m][co] : 0), act_lo)  from the float32 accumulators,
+ * stored once in `dtype`.  No pre-normalisation tensor, no statistics rows.  x, wp, bias and the geometry: as pcrl_conv2d_fwd (every geometry it
+ * computes: `up`, stride 2, 1x1, 7x7, float32); scale, shift: Co floats (gamma / sqrt(running_var + eps), beta - running_mean * scale); residual:
+ * NULL or [M][Co] in the layout and dtype of the output; act: PCRL_ACT_RELU or PCRL_ACT_NONE (other codes are an error).
+ * Kernels: the one pcrl_conv2d_fwd's route names, with the epilogue (gather, narrow, 4x8x8 brick; wide brick without a residual); a wide-brick
+ * call WITH a residual -- that epilogue has no residual operand -- is computed by the gather kernel in one pass.
+ * `pcrl_conv2d_fwd_affine_fused` (host only, the same route function) -> 1 where this one pass replaces pcrl_conv2d_fwd + pcrl_bn_act_apply
+ * (+ pcrl_add_relu_fwd) on the same kernel family, 0 where the caller should keep separate passes (a wide-brick layer with a residual: the call
+ * without the residual is fused, pcrl_add_relu_fwd stays). */
+int64_t pcrl_conv2d_fwd_affine_fused(int N, int Hi, int Wi, int CiP, int Co, int KH, int KW, int stride, int pad, int up, int has_residual, int dtype);
+int pcrl_conv2d_fwd_affine(const void* x, const void* wp, const float* bias, const float* scale, const float* shift, const void* residual, void* a,
+                           int N, int Hi, int Wi, int CiP, int Co, int KH, int KW, int stride, int pad, int up, int act, int dtype, pcrl_stream_t stream);
 /* data gradient of a 3x3 / stride 1 / pad 1 convolution that read its input through the nearest x2 upsample (decoder conv1,
  * models/pcrlv2_model.py:114) INCLUDING the upsample's backward (aten::convolution_backward's input gradient + aten::upsample_nearest2d_backward):
  * dx[N][Hc][Wc][Ci] = 2 x 2 block sums of the fine-resolution gradient, which is never stored.  dy: [N][2Hc][2Wc][CoP]; wp_dgrad as for

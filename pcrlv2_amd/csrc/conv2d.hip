@@ -45,14 +45,22 @@ struct C2Params {
   int placed;          // output row (n, oh, ow) is stored at pixel (oh * 2 + pa, ow * 2 + pb) of an [N][Hf][Wf] tensor (stride-2 data gradient)
   int pa, pb, Hf, Wf;
   int64_t M;
+  // AFF instantiations only (inference forward, pcrl_conv2d_fwd_affine): the epilogue stores a = max(scale[co] * (acc + bias[co]) + shift[co] + res[m][co], act_lo)
+  // -- eval-mode BatchNorm2d (ops.bn_eval_coef's scale / shift), the BasicBlock's identity (res: [M][Nc] in T, or null) and the activation (act_lo = 0: ReLU,
+  // -inf: none) from the float32 accumulators; no pre-normalisation tensor, no statistics rows.
+  const float* scale;
+  const float* shift;
+  const void* res;
+  float act_lo;
 };
 
 
 // NSM > 0: burst variant for layers with at most NSM K-steps (16-channel layers at full resolution, the 1x1 / 3-channel heads): all
 // K-steps are loaded up front into NSM register sets, so a block waits for global memory once instead of once per step -- these
 // launches are 131 072 blocks of a few hundred MFMA cycles each and were bound by exactly that latency chain.
-template <typename T, int BN, int MODE, int NSM = 0>
+template <typename T, int BN, int MODE, int NSM = 0, bool AFF = false>
 __global__ void __launch_bounds__(256, PCRL_OCC2) conv2d_kernel(const C2Params p) {
+  static_assert(!AFF || MODE == C2_FWD, "the inference epilogue exists for the forward only");
   constexpr int BM = PCRL_CONV_BM;
   using TL = Tile<T>;
   using MM = Mma<T>;
@@ -226,6 +234,7 @@ __global__ void __launch_bounds__(256, PCRL_OCC2) conv2d_kernel(const C2Params p
   T* __restrict__ Y = reinterpret_cast<T*>(p.y);
   float* __restrict__ Yf = reinterpret_cast<float*>(p.y);
   float s1[FN], s2[FN], bv[FN];
+  float asc[FN], ash[FN];   // AFF: the eval-mode BatchNorm coefficients of this lane's FN channels
   bool cok[FN];
 #pragma unroll
   for (int j = 0; j < FN; ++j) {
@@ -234,7 +243,12 @@ __global__ void __launch_bounds__(256, PCRL_OCC2) conv2d_kernel(const C2Params p
     s1[j] = 0.f;
     s2[j] = 0.f;
     bv[j] = (p.bias && cok[j]) ? p.bias[col] : 0.f;
+    if (AFF) {
+      asc[j] = cok[j] ? p.scale[col] : 0.f;
+      ash[j] = cok[j] ? p.shift[col] : 0.f;
+    }
   }
+  const T* __restrict__ R = reinterpret_cast<const T*>(p.res);
 #pragma unroll
   for (int i = 0; i < FM; ++i) {
 #pragma unroll
@@ -251,18 +265,24 @@ __global__ void __launch_bounds__(256, PCRL_OCC2) conv2d_kernel(const C2Params p
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
           if (cok[j]) {
-            const float v = acc[i][j][r] + bv[j];
+            float v = acc[i][j][r] + bv[j];
             const int64_t o = orow * p.Nc + n0 + wn * (BN / 2) + j * 16 + lr;
-            if (p.out_f32) Yf[o] = v;
-            else Y[o] = from_f<T>(v);
-            s1[j] += v;
-            s2[j] += v * v;
+            if (AFF) {
+              v = fmaf(asc[j], v, ash[j]);
+              if (R) v += to_f(R[o]);   // kernel argument: uniform
+              Y[o] = from_f<T>(fmaxf(v, p.act_lo));
+            } else {
+              if (p.out_f32) Yf[o] = v;
+              else Y[o] = from_f<T>(v);
+              s1[j] += v;
+              s2[j] += v * v;
+            }
           }
         }
       }
     }
   }
-  if (p.stats) {
+  if (!AFF && p.stats) {
     float* red = reinterpret_cast<float*>(smem);
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
@@ -334,29 +354,42 @@ int ilog2_exact(int v) {
   return s;
 }
 
-template <typename T, int MODE> int launch_bn(const C2Params& p, int NcP, hipStream_t stream) {
+template <typename T, int MODE, bool AFF = false> int launch_bn(const C2Params& p, int NcP, hipStream_t stream) {
   using TL = Tile<T>;
   const unsigned gx = (unsigned)((p.M + PCRL_CONV_BM - 1) / PCRL_CONV_BM);
   // 128-column tiles (two waves per SIMD) unless the grid they give is small: below 512 blocks the 64-column tile (four waves per SIMD, twice the
   // blocks) is faster -- measured on the local views' 12^2 / 6^2 / 3^2 maps (49 -> 45, 52 -> 48, 86 -> 69 us), slower on the large grids (90 -> 105 us)
-  if (NcP % 128 == 0 && (int64_t)gx * (NcP / 128) >= 512) {
-    hipLaunchKernelGGL((conv2d_kernel<T, 128, MODE>), dim3(gx, NcP / 128), dim3(256), 2 * (size_t)(PCRL_CONV_BM + 128) * TL::ROWB, stream, p);
-  } else if (NcP % 64 == 0) {
-    hipLaunchKernelGGL((conv2d_kernel<T, 64, MODE>), dim3(gx, NcP / 64), dim3(256), 2 * (size_t)(PCRL_CONV_BM + 64) * TL::ROWB, stream, p);
+  // (the float32 inference form has no 128-column tile: with the epilogue's coefficients it does not fit 256 registers; float32 is the reference-check path)
+  constexpr bool tile128 = !(AFF && sizeof(T) == 4);
+  if constexpr (tile128) {
+    if (NcP % 128 == 0 && (int64_t)gx * (NcP / 128) >= 512) {
+      hipLaunchKernelGGL((conv2d_kernel<T, 128, MODE, 0, AFF>), dim3(gx, NcP / 128), dim3(256), 2 * (size_t)(PCRL_CONV_BM + 128) * TL::ROWB, stream, p);
+      return pcrl_check_launch("conv2d");
+    }
+  }
+  if (NcP % 64 == 0) {
+    hipLaunchKernelGGL((conv2d_kernel<T, 64, MODE, 0, AFF>), dim3(gx, NcP / 64), dim3(256), 2 * (size_t)(PCRL_CONV_BM + 64) * TL::ROWB, stream, p);
   } else {
     const int S = p.Kpad / 32;
     const size_t lds = 2 * (size_t)(PCRL_CONV_BM + 32) * TL::ROWB;
-    if (S <= 1) hipLaunchKernelGGL((conv2d_kernel<T, 32, MODE, 1>), dim3(gx, NcP / 32), dim3(256), lds, stream, p);
-    else if (S <= 3) hipLaunchKernelGGL((conv2d_kernel<T, 32, MODE, 3>), dim3(gx, NcP / 32), dim3(256), lds, stream, p);
-    else if (S <= 5) hipLaunchKernelGGL((conv2d_kernel<T, 32, MODE, 5>), dim3(gx, NcP / 32), dim3(256), lds, stream, p);
-    else hipLaunchKernelGGL((conv2d_kernel<T, 32, MODE>), dim3(gx, NcP / 32), dim3(256), lds, stream, p);
+    if (S <= 1) hipLaunchKernelGGL((conv2d_kernel<T, 32, MODE, 1, AFF>), dim3(gx, NcP / 32), dim3(256), lds, stream, p);
+    else if (S <= 3) hipLaunchKernelGGL((conv2d_kernel<T, 32, MODE, 3, AFF>), dim3(gx, NcP / 32), dim3(256), lds, stream, p);
+    else if (S <= 5) hipLaunchKernelGGL((conv2d_kernel<T, 32, MODE, 5, AFF>), dim3(gx, NcP / 32), dim3(256), lds, stream, p);
+    else hipLaunchKernelGGL((conv2d_kernel<T, 32, MODE, 0, AFF>), dim3(gx, NcP / 32), dim3(256), lds, stream, p);
   }
   return pcrl_check_launch("conv2d");
 }
 
+// the inference epilogue's operands (C2Params: scale, shift, res, act_lo)
+struct C2Affine {
+  const float *scale, *shift;
+  const void* res;
+  float act_lo;
+};
+
 int conv2d_common(const char* what, int mode, const void* src, const void* wp, const float* bias, void* out, float* stats, int N, int Hs, int Ws,
                   int Cs, int Ho, int Wo, int Nc, int KH, int KW, int stride, int pad, int up, int out_f32, int dtype, hipStream_t stream,
-                  int placed = 0, int pa = 0, int pb = 0, int Hf = 0, int Wf = 0) {
+                  int placed = 0, int pa = 0, int pb = 0, int Hf = 0, int Wf = 0, const C2Affine* aff = nullptr) {
   PCRL_REQUIRE(src && wp && out, "%s: null pointer", what);
   PCRL_REQUIRE(N > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0 && Nc > 0, "%s: bad dims", what);
   PCRL_REQUIRE(dtype == PCRL_F32 || dtype == PCRL_BF16, "%s: bad dtype %d", what, dtype);
@@ -375,7 +408,12 @@ int conv2d_common(const char* what, int mode, const void* src, const void* wp, c
   p.out_f32 = out_f32;
   p.placed = placed; p.pa = pa; p.pb = pb; p.Hf = Hf; p.Wf = Wf;
   p.M = (int64_t)N * Ho * Wo;
+  p.scale = aff ? aff->scale : nullptr; p.shift = aff ? aff->shift : nullptr; p.res = aff ? aff->res : nullptr; p.act_lo = aff ? aff->act_lo : 0.f;
   const int NcP = (Nc + 31) / 32 * 32;
+  if (aff) {
+    PCRL_REQUIRE(mode == C2_FWD && !out_f32 && !stats && !placed, "%s: the inference epilogue is a plain forward in the activation dtype", what);
+    return dtype == PCRL_BF16 ? launch_bn<bf16, C2_FWD, true>(p, NcP, stream) : launch_bn<float, C2_FWD, true>(p, NcP, stream);
+  }
   if (dtype == PCRL_BF16) return mode == C2_FWD ? launch_bn<bf16, C2_FWD>(p, NcP, stream) : launch_bn<bf16, C2_DGRAD>(p, NcP, stream);
   return mode == C2_FWD ? launch_bn<float, C2_FWD>(p, NcP, stream) : launch_bn<float, C2_DGRAD>(p, NcP, stream);
 }
@@ -482,6 +520,36 @@ extern "C" int pcrl_conv2d_fwd(const void* x, const void* wp, const float* bias,
   }
   return conv2d_common("conv2d_fwd", C2_FWD, x, wp, bias, y, stats_partial, N, Hi, Wi, CiP, Ho, Wo, Co, KH, KW, stride, pad, up, out_f32, dtype,
                        as_stream(stream));
+}
+
+// ---- inference forward: convolution + eval-mode BatchNorm2d (+ residual) + activation in one pass ----
+// Fused (one pass on the family the unfused convolution runs on): the gather, narrow and 4x8x8-brick routes with or without a residual, the wide-brick
+// route without one.  Not fused: a wide-brick layer WITH a residual (that epilogue has no residual operand, conv_brick16.h) -- the caller runs the call
+// without the residual and keeps the add pass; pcrl_conv2d_fwd_affine itself still computes such a call, on the gather kernel in one pass.
+static bool conv2d_affine_on_route(Conv2dRoute route, bool has_residual) { return route != CONV2D_BRICK16 || !has_residual; }
+extern "C" int64_t pcrl_conv2d_fwd_affine_fused(int N, int Hi, int Wi, int CiP, int Co, int KH, int KW, int stride, int pad, int up, int has_residual, int dtype) {
+  if (N <= 0 || Hi <= 0 || Wi <= 0 || CiP <= 0 || Co <= 0 || KH <= 0 || KW <= 0 || stride < 1 || stride > 2) return 0;
+  return conv2d_affine_on_route(conv2d_fwd_route(N, Hi, Wi, CiP, Co, KH, KW, stride, pad, up, 0, dtype).route, has_residual != 0);
+}
+extern "C" int pcrl_conv2d_fwd_affine(const void* x, const void* wp, const float* bias, const float* scale, const float* shift, const void* residual, void* a,
+                                      int N, int Hi, int Wi, int CiP, int Co, int KH, int KW, int stride, int pad, int up, int act, int dtype,
+                                      pcrl_stream_t stream) {
+  PCRL_REQUIRE(x && wp && scale && shift && a, "conv2d_fwd_affine: null pointer");
+  PCRL_REQUIRE(N > 0 && Hi > 0 && Wi > 0 && CiP > 0 && Co > 0, "conv2d_fwd_affine: bad dims");
+  PCRL_REQUIRE(dtype == PCRL_F32 || dtype == PCRL_BF16, "conv2d_fwd_affine: bad dtype %d", dtype);
+  PCRL_REQUIRE(act == PCRL_ACT_RELU || act == PCRL_ACT_NONE, "conv2d_fwd_affine: activation %d has no fused form (ReLU or none)", act);
+  const float act_lo = act == PCRL_ACT_RELU ? 0.f : -INFINITY;
+  const Conv2dFwd f = conv2d_fwd_route(N, Hi, Wi, CiP, Co, KH, KW, stride, pad, up, 0, dtype);
+  if (conv2d_affine_on_route(f.route, residual != nullptr)) {
+    if (f.route == CONV2D_BRICK16) return pcrl_brick16_conv2d_affine_launch(x, wp, bias, scale, shift, act_lo, a, N, f.Ho, f.Wo, CiP, Co, as_stream(stream));
+    if (f.route == CONV2D_BRICK8)
+      return pcrl_brick_conv2d_affine_launch(x, wp, bias, scale, shift, residual, act_lo, a, N, f.Ho, f.Wo, CiP, Co, up, as_stream(stream));
+    if (f.route == CONV2D_NARROW)
+      return pcrl_conv2d_narrow_affine_launch(x, wp, bias, scale, shift, residual, act_lo, a, N, f.Ho, f.Wo, CiP, Co, KH, up, as_stream(stream));
+  }
+  const C2Affine aff{scale, shift, residual, act_lo};
+  return conv2d_common("conv2d_fwd_affine", C2_FWD, x, wp, bias, a, nullptr, N, Hi, Wi, CiP, f.Ho, f.Wo, Co, KH, KW, stride, pad, up, 0, dtype, as_stream(stream),
+                       0, 0, 0, 0, 0, &aff);
 }
 
 extern "C" int64_t pcrl_conv2d_fwd_stats_only_ok(int N, int Hi, int Wi, int CiP, int Co, int KH, int KW, int stride, int pad, int up, int out_f32, int dtype) {

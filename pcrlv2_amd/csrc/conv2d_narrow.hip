@@ -34,6 +34,12 @@ struct NarrowConvParams {
   int ks;             // 1 (pad 0) or 3 (pad 1)
   int Ktot, Kpad;
   int npatch, per;    // patches in all, patches per block (a block walks a contiguous range)
+  // AFF instantiations only (inference forward, pcrl_conv2d_fwd_affine): y = max(scale[co] * (acc + bias[co]) + shift[co] + res[px][co], act_lo) in bf16 --
+  // eval-mode BatchNorm2d, an optional residual in the layout of y (or null) and the activation (act_lo = 0: ReLU, -inf: none); no statistics
+  const float* scale;
+  const float* shift;
+  const bf16* res;
+  float act_lo;
 };
 
 // Round 4 form.  What changed against the one-patch-per-block kernel (351 us for 16 -> 16 channels at 512^2 x 64 images, where HBM needs 180):
@@ -46,8 +52,9 @@ struct NarrowConvParams {
 //   * RED2: the data gradient of a convolution that read its input through the nearest x2 upsample (decoder conv1, pcrlv2_model.py:114): the 2 x 2
 //     sum of F.interpolate's backward is taken on the float accumulators (vertical pair = two fragments of the lane, horizontal pair = the
 //     neighbouring lane) and the COARSE tensor is stored -- the fine-resolution gradient (1 GB at block 4) is never written or read.
-template <int CS, int NF, int NS, bool RED2>   // source channels (8/16/32), output fragments (Nc <= 16 * NF), K-steps (Kpad / 32)
+template <int CS, int NF, int NS, bool RED2, bool AFF = false>   // source channels (8/16/32), output fragments (Nc <= 16 * NF), K-steps (Kpad / 32)
 __global__ void __launch_bounds__(256, PCRL_OCC2) conv2d_narrow_kernel(const NarrowConvParams p) {
+  static_assert(!AFF || (!RED2 && NARROW_TRANSPOSED), "the inference epilogue exists for the transposed forward only");
   constexpr int VPC = CS / 8;
   constexpr int XPIECES = NHP * VPC, XP = (XPIECES + 255) / 256;
   constexpr int CSH = CS == 8 ? 3 : (CS == 16 ? 4 : 5);
@@ -97,6 +104,17 @@ __global__ void __launch_bounds__(256, PCRL_OCC2) conv2d_narrow_kernel(const Nar
       bv[nf][r] = (p.bias && co < p.Nc) ? p.bias[co] : 0.f;
       s1[nf][r] = s2[nf][r] = 0.f;
     }
+  float asc[NF][4], ash[NF][4];   // AFF: the eval-mode BatchNorm coefficients of this lane's channels
+  if (AFF) {
+#pragma unroll
+    for (int nf = 0; nf < NF; ++nf)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int co = nf * 16 + 4 * lg + r;
+        asc[nf][r] = co < p.Nc ? p.scale[co] : 0.f;
+        ash[nf][r] = co < p.Nc ? p.shift[co] : 0.f;
+      }
+  }
 
   u32x4 rx[XP];
   uint32_t xok = 0;
@@ -198,12 +216,27 @@ __global__ void __launch_bounds__(256, PCRL_OCC2) conv2d_narrow_kernel(const Nar
 #pragma unroll
         for (int nf = 0; nf < NF; ++nf) {
           const int c0 = nf * 16 + 4 * lg;
-          float v[4];
+          float v[4], rv[4] = {0.f, 0.f, 0.f, 0.f};
+          if (AFF && p.res && c0 < p.Nc) {   // p.res: kernel argument, uniform; one 8-byte read where the store is one 8-byte write
+            if (vec_ok) {
+              const bf16x4 t = *reinterpret_cast<const bf16x4*>(p.res + row * p.Nc + c0);
+#pragma unroll
+              for (int r = 0; r < 4; ++r) rv[r] = (float)t[r];
+            } else {
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                if (c0 + r < p.Nc) rv[r] = (float)p.res[row * p.Nc + c0 + r];
+            }
+          }
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             v[r] = acc[mf][nf][r] + bv[nf][r];
-            s1[nf][r] += v[r];
-            s2[nf][r] += v[r] * v[r];
+            if (AFF) {
+              v[r] = fmaxf(fmaf(asc[nf][r], v[r], ash[nf][r]) + rv[r], p.act_lo);
+            } else {
+              s1[nf][r] += v[r];
+              s2[nf][r] += v[r] * v[r];
+            }
           }
           if (c0 < p.Nc && p.y) {      // p.y == nullptr (kernel argument: uniform): statistics only, the output has no reader (pcrl_conv2d_fwd with y = NULL)
             const int64_t o = row * p.Nc + c0;
@@ -265,7 +298,7 @@ __global__ void __launch_bounds__(256, PCRL_OCC2) conv2d_narrow_kernel(const Nar
   }
 #undef NC_LOAD
 #undef NC_STORE
-  if (!RED2 && p.stats) {
+  if (!RED2 && !AFF && p.stats) {
 #if NARROW_TRANSPOSED
 #pragma unroll
     for (int nf = 0; nf < NF; ++nf)
@@ -314,9 +347,15 @@ NarrowConvPlan narrow_conv_plan(int64_t npatch) {
   return NarrowConvPlan{(int)((npatch + per - 1) / per), per};
 }
 
-template <int CS, int NF> int launch_ns(const NarrowConvParams& p, unsigned blocks, bool red2, hipStream_t st) {
+template <int CS, int NF> int launch_ns(const NarrowConvParams& p, unsigned blocks, bool red2, hipStream_t st, bool aff = false) {
   constexpr int NS3 = CS == 8 ? 3 : (CS == 16 ? 5 : 9);   // K-steps of the 3x3 kernel; the 1x1 kernel has one
   const int ns = p.Kpad / 32;
+  if (aff) {
+    if (ns == 1) hipLaunchKernelGGL((conv2d_narrow_kernel<CS, NF, 1, false, true>), dim3(blocks), dim3(256), 0, st, p);
+    else if (ns == NS3) hipLaunchKernelGGL((conv2d_narrow_kernel<CS, NF, NS3, false, true>), dim3(blocks), dim3(256), 0, st, p);
+    else return pcrl_fail(PCRL_EINVAL, "conv2d_narrow: unsupported K (%d steps)", ns);
+    return pcrl_check_launch("conv2d_narrow_affine");
+  }
   if (red2) {
     if (ns != NS3) return pcrl_fail(PCRL_EINVAL, "conv2d_narrow: the upsample-backward form is 3x3 only");
     hipLaunchKernelGGL((conv2d_narrow_kernel<CS, NF, NS3, true>), dim3(blocks), dim3(256), 0, st, p);
@@ -344,10 +383,24 @@ int pcrl_conv2d_narrow_launch(const void* x, const void* wp, const float* bias, 
   const NarrowConvPlan pl = narrow_conv_plan(npatch);
   if (red2 && (bias || stats || out_f32 || up || ks != 3)) return pcrl_fail(PCRL_EINVAL, "conv2d_narrow: bad arguments for the upsample-backward form");
   NarrowConvParams p{(const bf16*)x, (const bf16*)wp, bias, y, stats, N, H, W, up, Nc, out_f32, ks, ks * ks * Cs, (ks * ks * Cs + 31) / 32 * 32,
-                     (int)npatch, pl.per};
+                     (int)npatch, pl.per, nullptr, nullptr, nullptr, 0.f};
   const unsigned blocks = (unsigned)pl.blocks;
   const bool two = Nc > 16;
   if (Cs == 8) return two ? launch_ns<8, 2>(p, blocks, red2, stream) : launch_ns<8, 1>(p, blocks, red2, stream);
   if (Cs == 16) return two ? launch_ns<16, 2>(p, blocks, red2, stream) : launch_ns<16, 1>(p, blocks, red2, stream);
   return two ? launch_ns<32, 2>(p, blocks, red2, stream) : launch_ns<32, 1>(p, blocks, red2, stream);
+}
+
+// inference forward (AFF): convolution + eval-mode BatchNorm2d (+ residual) + activation, bf16 output, one pass
+int pcrl_conv2d_narrow_affine_launch(const void* x, const void* wp, const float* bias, const float* scale, const float* shift, const void* res, float act_lo,
+                                     void* a, int N, int H, int W, int Cs, int Nc, int ks, int up, hipStream_t stream) {
+  const int64_t npatch = (int64_t)N * (H / PH) * (W / PW);
+  const NarrowConvPlan pl = narrow_conv_plan(npatch);
+  NarrowConvParams p{(const bf16*)x, (const bf16*)wp, bias, a, nullptr, N, H, W, up, Nc, 0, ks, ks * ks * Cs, (ks * ks * Cs + 31) / 32 * 32,
+                     (int)npatch, pl.per, scale, shift, (const bf16*)res, act_lo};
+  const unsigned blocks = (unsigned)pl.blocks;
+  const bool two = Nc > 16;
+  if (Cs == 8) return two ? launch_ns<8, 2>(p, blocks, false, stream, true) : launch_ns<8, 1>(p, blocks, false, stream, true);
+  if (Cs == 16) return two ? launch_ns<16, 2>(p, blocks, false, stream, true) : launch_ns<16, 1>(p, blocks, false, stream, true);
+  return two ? launch_ns<32, 2>(p, blocks, false, stream, true) : launch_ns<32, 1>(p, blocks, false, stream, true);
 }

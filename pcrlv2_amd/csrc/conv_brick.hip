@@ -69,6 +69,12 @@ struct BrickParams {
   int cshift;
   int bd, bh, bw;        // bit of the phase / parity number (d = 4, h = 2, w = 1 of the MEMORY axes) that belongs to the brick's d, h, w axis: 2, 1, 0
   int fsd, fsh, fsw;     // strides, in fine voxels, of the brick's axes on the fine grid: 4 H W, 2 W, 1
+  // AFF instantiations only (2D inference forward, pcrl_conv2d_fwd_affine; KD = 1, MODE 0): the epilogue stores
+  // a = max(aff_scale[co] * (acc + bias[co]) + aff_shift[co] + res[voxel][co], act_lo) -- eval-mode BatchNorm2d, the BasicBlock's identity (layout of y, or
+  // null) and the activation (act_lo = 0: ReLU, -inf: none) from the float32 accumulators; no pre-normalisation tensor, no statistics rows.
+  const float *aff_scale, *aff_shift;
+  const bf16* res;
+  float act_lo;
 };
 
 // Weight tile [64 co][32 k]: a fragment read takes 16 CONSECUTIVE rows -> same swizzle as conv_igemm.hip's Tile<bf16>.
@@ -86,8 +92,9 @@ __device__ __forceinline__ int hoff_h(int row, int slot) {
   return row * 64 + ((slot ^ (((row >> 2) & 1) << 1)) << 4);
 }
 
-template <int BN, int KD, int MODE = 0>   // BN = output channels per block: 64, or 32 for the Co = 32 data gradient (wave tile 64 voxels x BN)
+template <int BN, int KD, int MODE = 0, bool AFF = false>   // BN = output channels per block: 64, or 32 for the Co = 32 data gradient (wave tile 64 voxels x BN)
 __global__ void __launch_bounds__(256, 2) brick_conv_kernel(const BrickParams p) {
+  static_assert(!AFF || (KD == 1 && MODE == 0), "the inference epilogue exists for the 2D forward only");
   using BG = BrickGeom<KD>;
   static_assert(MODE == 0 || KD == 3, "the composed modes are 3-D");
   constexpr bool UPCF = MODE == 1, UPCD = MODE == 2;
@@ -382,6 +389,15 @@ __global__ void __launch_bounds__(256, 2) brick_conv_kernel(const BrickParams p)
     s2[j] = 0.f;
     bv[j] = (!UPCF && p.bias) ? p.bias[n0 + j * 16 + lr] : 0.f;
   }
+  float asc[FN], ash[FN];   // AFF: the eval-mode BatchNorm coefficients of this lane's FN channels
+  if (AFF) {
+#pragma unroll
+    for (int j = 0; j < FN; ++j) {
+      asc[j] = p.aff_scale[n0 + j * 16 + lr];
+      ash[j] = p.aff_shift[n0 + j * 16 + lr];
+    }
+  }
+  const int64_t rdelta = (AFF && p.res) ? reinterpret_cast<const char*>(p.res) - reinterpret_cast<const char*>(p.y) : 0;   // the identity has the layout of y
   const int uch0 = UPCF ? n0 - uph * p.upc : n0;   // first channel of this tile (inside its phase)
   const int ypitch = UPCF ? p.upc : p.Nc;
   // byte steps of the output along the brick's h and w axes (composed forward: a coarse step is two fine voxels)
@@ -406,14 +422,21 @@ __global__ void __launch_bounds__(256, 2) brick_conv_kernel(const BrickParams p)
       char* const yrow = ybase + (int64_t)(2 * fm) * HS + (int64_t)r * WS;   // scalar
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
-        const float val = acc[fm][j][r] + bv[j];
+        float val = acc[fm][j][r] + bv[j];
+        if (AFF) {
+          val = fmaf(asc[j], val, ash[j]);
+          if (p.res) val += (float)*reinterpret_cast<const bf16*>(yrow + rdelta + yl + j * 32);   // kernel argument: uniform
+          val = fmaxf(val, p.act_lo);
+        }
         if (!(BRICK_ABL & 1) || val == 12345.678f) *reinterpret_cast<bf16*>(yrow + yl + j * 32) = (bf16)val;
-        s1[j] += val;
-        s2[j] += val * val;
+        if (!AFF) {
+          s1[j] += val;
+          s2[j] += val * val;
+        }
       }
     }
   }
-  if (p.stats) {
+  if (!AFF && p.stats) {
     float* red = reinterpret_cast<float*>(smem);  // [4 waves][64 ch][2]; the loop ended with a barrier
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
@@ -496,6 +519,18 @@ int pcrl_brick_conv2d_launch(const void* x, const void* wp, const float* bias, v
   if (Co % 64 == 0) hipLaunchKernelGGL((brick_conv_kernel<64, 1>), dim3(bricks, Co / 64), dim3(256), HB + 3 * 64 * 64, stream, p);
   else hipLaunchKernelGGL((brick_conv_kernel<32, 1>), dim3(bricks, Co / 32), dim3(256), HB + 3 * 32 * 64, stream, p);
   return pcrl_check_launch("brick_conv2d");
+}
+
+// inference forward (AFF): the same convolution with eval-mode BatchNorm2d (+ residual) + activation in the epilogue, one pass
+int pcrl_brick_conv2d_affine_launch(const void* x, const void* wp, const float* bias, const float* scale, const float* shift, const void* res, float act_lo,
+                                    void* a, int N, int H, int W, int Ci, int Co, int up, hipStream_t stream) {
+  constexpr int HB = BrickGeom<1>::HALO_BYTES;
+  BrickParams p{(const bf16*)x, (const bf16*)wp, bias, (bf16*)a, nullptr, 1, N, H, W, Ci, Co, up, 0, H * W, W, 1, 9, 3, 1};
+  p.aff_scale = scale; p.aff_shift = shift; p.res = (const bf16*)res; p.act_lo = act_lo;
+  const unsigned bricks = (unsigned)pcrl_brick_conv2d_rows(N, H, W);
+  if (Co % 64 == 0) hipLaunchKernelGGL((brick_conv_kernel<64, 1, 0, true>), dim3(bricks, Co / 64), dim3(256), HB + 3 * 64 * 64, stream, p);
+  else hipLaunchKernelGGL((brick_conv_kernel<32, 1, 0, true>), dim3(bricks, Co / 32), dim3(256), HB + 3 * 32 * 64, stream, p);
+  return pcrl_check_launch("brick_conv2d_affine");
 }
 
 // ---- composed ConvTranspose3d -> Conv3d operator (upconv_fused.hip) on the 4 x 8 x 8 brick: forward and data gradient ----

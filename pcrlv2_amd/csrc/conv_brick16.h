@@ -88,7 +88,8 @@ struct Brick16Params {
   const float *bn_scale, *bn_shift, *bn_mean, *bn_rstd;
   // INF instantiations only (inference forward, conv_brick16_inf.hip): the epilogue stores a = max(bn_scale[co] * (acc + bias[co]) + bn_shift[co], act_lo)
   // -- eval-mode BatchNorm (ops.bn_eval_coef's scale / shift) and the activation (act_lo = 0: ReLU, -inf: none) from the float32 accumulators; no
-  // pre-normalisation tensor, no statistics rows.
+  // pre-normalisation tensor, no statistics rows.  (No residual operand: read in this epilogue, a BasicBlock's identity spilled 5-37 registers of the
+  // 64-channel form in three formulations; pcrl_conv2d_fwd_affine adds the identity on this route in a pass of its own.)
   float act_lo;
 };
 
@@ -124,7 +125,7 @@ __device__ __forceinline__ void lds_dma16_masked(uint64_t base, uint32_t voff, u
 // an axis (BITH / BITW) and the border class (CLS) know the difference; rows still go through LDS one 64-byte slice per voxel.
 template <int BN, int MODE = 0, int PERM = 0, int NW = 4, bool BNR = false, bool INF = false>
 __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) brick16_conv_kernel(const Brick16Params p) {
-  static_assert(!INF || (MODE == 0 && NW == 4 && !BNR), "the inference epilogue exists for the plain 4-plane forward only");
+  static_assert(!INF || ((MODE == 0 || MODE == 3) && NW == 4 && !BNR), "the inference epilogue exists for the plain 4-plane forward only (3D, and the 2D path's 3x3 form)");
   static_assert(!BNR || ((MODE == 0 || MODE == 3) && NW == 4), "the BatchNorm-reduce epilogue exists for the plain 4-plane data gradient only (3D, and the 2D path's 3x3 form)");
   using G = B16Geom<NW>;
   constexpr int ROWS = G::ROWS, NDMA = G::NDMA, HALO_BYTES = G::HALO_BYTES, HD = G::HD;

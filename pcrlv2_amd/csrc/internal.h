@@ -38,6 +38,8 @@ int pcrl_brick_conv_launch(const void* x, const void* wp, const float* bias, voi
 bool pcrl_brick_conv2d_eligible(int N, int H, int W, int Ci, int Co, int dtype);
 int64_t pcrl_brick_conv2d_rows(int N, int H, int W);
 int pcrl_brick_conv2d_launch(const void* x, const void* wp, const float* bias, void* y, float* stats, int N, int H, int W, int Ci, int Co, int up, hipStream_t stream);
+int pcrl_brick_conv2d_affine_launch(const void* x, const void* wp, const float* bias, const float* scale, const float* shift, const void* res, float act_lo,
+                                    void* a, int N, int H, int W, int Ci, int Co, int up, hipStream_t stream);
 bool pcrl_brick8_upc_fwd_eligible(int N, int D, int H, int W, int Ci, int Co, int dtype);
 int pcrl_brick8_upc_fwd_launch(const void* x, const void* w3, const float* bias_tab, void* y0, float* stats, int N, int D, int H, int W, int Ci, int Co, hipStream_t stream);
 bool pcrl_brick8_upc_dgrad_eligible(int N, int D, int H, int W, int Ci, int Co, int dtype);
@@ -60,6 +62,8 @@ int pcrl_brick16_upc_dgrad_launch(const void* dy0, const void* wd3, void* dx, in
 // ---- conv_brick16_inf.hip: convolution + eval-mode BatchNorm + activation ------------------------------------------------------------
 int pcrl_brick16_conv_affine_launch(const void* x, const void* wp, const float* bias, const float* scale, const float* shift, float act_lo, void* a,
                                     int N, int D, int H, int W, int Ci, int Co, hipStream_t stream);
+int pcrl_brick16_conv2d_affine_launch(const void* x, const void* wp, const float* bias, const float* scale, const float* shift, float act_lo, void* a,
+                                      int N, int H, int W, int Ci, int Co, hipStream_t stream);
 
 // ---- conv_brick16_bnr.hip: data gradient + first pass of the BatchNorm backward of the layer below ----------------------------------
 int pcrl_brick16_dgrad_bnred_launch(const void* dy, const void* wp, void* dx, const void* bn_y, const float* scale, const float* shift, const float* mean,
@@ -87,6 +91,8 @@ int pcrl_to1_brick_launch(const void* x, const float* w_ref, const float* bias, 
 bool pcrl_conv2d_narrow_eligible(int N, int H, int W, int Cs, int Nc, int ks, int dtype);
 int64_t pcrl_conv2d_narrow_rows(int N, int H, int W);
 int pcrl_conv2d_narrow_launch(const void* x, const void* wp, const float* bias, void* y, float* stats, int N, int H, int W, int Cs, int Nc, int ks, int up, int out_f32, int red2, hipStream_t stream);
+int pcrl_conv2d_narrow_affine_launch(const void* x, const void* wp, const float* bias, const float* scale, const float* shift, const void* res, float act_lo,
+                                     void* a, int N, int H, int W, int Cs, int Nc, int ks, int up, hipStream_t stream);
 
 // ---- wgrad_brick.hip: LDS-halo brick weight-gradient kernel (3D; composed up-conv mode; 2D with the image index as depth, nkd = 1) ----
 bool pcrl_wgrad_brick_eligible(int N, int D, int H, int W, int Ci, int Co, int dtype);

@@ -385,6 +385,9 @@ class AugmentedLoader:
     def reset_rng(self):
         """The augmentation's device generator and its host companion back to the loader's seed (train_3d.validate: every validation pass
         draws the same augmentations)."""
+        if hasattr(self.augment, "reset_rng"):      # an augmentation that keeps its draws elsewhere (GpuChestAugment: a numpy Generator)
+            self.augment.reset_rng(self.seed)
+            return
         gen, host = getattr(self.augment, "gen", None), getattr(self.augment, "host_rng", None)
         if gen is not None:
             gen.manual_seed(self.seed)

@@ -29,7 +29,7 @@ import os
 import numpy as np
 import torch
 
-from .data import AugmentedLoader
+from .data import AugmentedLoader, _LazyLoaders, eval_shard
 
 NPARAM = 40            # PCRL_AUG2D_NPARAM: the per-view record of pcrl_aug2d_* (layout in include/pcrl_hip.h)
 (P_SRC, P_H, P_W, P_C, P_J, P_I, P_CW, P_CH, P_A0, P_A1, P_A2, P_A3, P_A4, P_A5, P_FLIP, P_GRAY, P_BLUR, P_BR, P_WW, P_FW,
@@ -205,6 +205,10 @@ class GpuChestAugment:
             raise RuntimeError("GpuChestAugment runs on the GPU (libpcrl_hip.so); there is no CPU fallback")
         self.rng = np.random.default_rng(seed)
 
+    def reset_rng(self, seed):
+        """The draws start over from `seed` (AugmentedLoader.reset_rng: every validation pass draws the same augmentations)."""
+        self.rng = np.random.default_rng(seed)
+
     def draw(self, dims):
         """-> (records [8B, NPARAM] int64, src offsets [B]): the B * 2 global views (view k * B + n is sample n's k-th), then the B * 6 local ones."""
         dims = np.asarray(dims, np.int64)
@@ -332,8 +336,25 @@ class ChestKind:
         return i == 1           # the dims stay on the host (they size the draws), the pixels go to the device
 
 
+def chest_valid_list(data_dir: str, list_file: str):
+    """The held-out images: the `name label...` lines of `list_file` (the reference ships train_val_txt/chest_valid.txt and never reads it) joined
+    to `data_dir`.  A missing list is an error -- the held-out set is never carved out of the training list; so is a listed file that is missing."""
+    if not os.path.exists(list_file):
+        raise SystemExit(f"--val_every needs the held-out image list {list_file} (--val_list), which does not exist; "
+                         "the held-out set is not carved out of the training list")
+    with open(list_file) as f:
+        names = [os.path.join(data_dir, line.split()[0]) for line in f if line.split()]
+    missing = [p for p in names if not os.path.isfile(p)]
+    if missing:
+        raise FileNotFoundError(f"{len(missing)} file(s) of {list_file} are not in {data_dir}, e.g. {missing[0]}")
+    if not names:
+        raise SystemExit(f"the held-out image list {list_file} is empty")
+    return names
+
+
 def chest_pretask_loaders(args, device=None):
-    """`DataGenerator(args).pcrlv2_chest_pretask()` (data.py:14-61): {'train': ..., 'eval': the same loader}."""
+    """`DataGenerator(args).pcrlv2_chest_pretask()` (data.py:14-61): {'train': ..., 'eval': the same loader}.  With --val_every > 0 'eval' is instead
+    this rank's contiguous shard of the held-out list (--val_list), unshuffled, built when somebody first asks for it (data._LazyLoaders)."""
     device = device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu")
     files = chest_file_list(args.data, args.ratio)
     print(f"total train images {len(files)}")
@@ -345,4 +366,14 @@ def chest_pretask_loaders(args, device=None):
     if world > 1:                     # equal shards, ragged last batch dropped: see data.luna_pretask_loaders
         files = files[:len(files) - len(files) % world]
     train = AugmentedLoader(files[rank::world], args.b, args.workers, device, True, seed + rank, drop_last=world > 1, kind=ChestKind(files))
-    return {"train": train, "eval": train}
+    if int(getattr(args, "val_every", 0) or 0) <= 0:
+        return {"train": train, "eval": train}
+    valid = eval_shard(chest_valid_list(args.data, getattr(args, "val_list", "./train_val_txt/chest_valid.txt")), rank, world)
+    print(f"valid images {len(valid)} (this rank)")
+
+    def make_eval():
+        ev = AugmentedLoader(valid, args.b, args.workers, device, False, seed, kind=ChestKind(valid))
+        ev.sharded = True       # built for this rank: train_2d.validate takes it whole
+        return ev
+
+    return _LazyLoaders(train, make_eval)

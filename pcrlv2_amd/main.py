@@ -43,9 +43,12 @@ _FLAGS = (
     ("resume", "", str, "checkpoint to continue from (model, momentum buffers, epoch)"),
     ("encoder_weights", "", str, "only with --d 2: local ResNet-18 state_dict (torchvision key names) for the encoder; empty = random init "
                                  "(the reference's smp.Unet('resnet18') downloads ImageNet weights, which an offline engine cannot)"),
-    ("val_every", 0, int, "only with --d 3: held-out validation (folds 7-9; a second synthetic stream with --data synthetic) after every N-th epoch; "
-                          "0 = never, like the reference"),
-    ("save_best", False, None, "with --val_every: write <model>_<n>_<phase>_<ratio>_best.pt whenever the validation total improves"),
+    ("val_every", 0, int, "held-out validation after every N-th epoch; 0 = never, like the reference.  --d 3: folds 7-9; --d 2: the images of --val_list; "
+                          "with --data synthetic a second generated stream"),
+    ("save_best", False, None, "with --val_every: write <model>_<n>_<phase>_<ratio>_best.pt whenever the validation total improves strictly "
+                               "(--d 3: the model's state_dict; --d 2: the encoder's, the 2D checkpoint layout) plus the metrics under 'val'"),
+    ("val_list", "./train_val_txt/chest_valid.txt", str, "only with --d 2 and --val_every > 0: the held-out image list (`name label...` lines, names relative to --data); "
+                                                        "a missing list is an error -- the held-out set is never carved out of the training list"),
     ("size2d", 224, int, "only with --d 2 --data synthetic: side of the global views (locals are 96x96)"),
 )
 
@@ -116,7 +119,12 @@ def get_dataloader(args):
     """`DataGenerator(args).pcrlv2_luna_pretask()` / `.pcrlv2_chest_pretask()` of the reference (data.py:63-99 / 14-61) -- `--data synthetic`:
     generated batches."""
     if args.data == 'synthetic' and args.d == 2:
-        return {'train': SyntheticChestLoader(args.b, args.steps_per_epoch, args.size2d, args.seed + int(os.environ.get("RANK", "0"))), 'eval': None}
+        rank = int(os.environ.get("RANK", "0"))
+        ev = None
+        if int(getattr(args, "val_every", 0) or 0) > 0:
+            ev = SyntheticChestLoader(args.b, args.steps_per_epoch, args.size2d, args.seed + 7919 + rank)      # another stream than any rank's training data
+            ev.sharded = True                                                                                # one stream per rank: nothing to cut
+        return {'train': SyntheticChestLoader(args.b, args.steps_per_epoch, args.size2d, args.seed + rank), 'eval': ev}
     if args.data == 'synthetic':
         rank = int(os.environ.get("RANK", "0"))
         ev = SyntheticLunaLoader(args.b, args.steps_per_epoch, args.seed + 7919 + rank)      # another stream than any rank's training data

@@ -36,6 +36,7 @@ class _Unit(_Counted):
         self.stride, self.pad, self.up, self.act = conv.stride[0], conv.padding[0], int(up), act
         self.compute_dtype = config.default_compute_dtype()
         self._packed = ops2d.PackedConv2d()
+        self._eval_coef = ops2d.EvalCoef()      # PCRLv2.infer: the eval-mode (scale, shift) of `bn`, cached until the statistics or the affine change
         self._pass_idx = 1
         self._init_counter([bn] if bn is not None else [])
 
@@ -189,6 +190,7 @@ class DecoderBlock(nn.Module, _Counted):
                                             nn.Linear(2 * out_channels, out_channels))
         self.compute_dtype = config.default_compute_dtype()
         self._pass_idx = 1
+        self._eval_coef_bn, self._eval_coef_ph = ops2d.EvalCoef(), ops2d.EvalCoef()      # PCRLv2.infer: eval-mode coefficients of the two BatchNorm1d
         self._u1 = _Unit(self.conv1[0], self.conv1[1], ACT_RELU, up=True)     # F.interpolate(nearest x2) fused into conv1's gather (:114)
         self._u2 = _Unit(self.conv2[0], self.conv2[1], ACT_RELU)
         ds = self.deep_supervision_head
@@ -354,9 +356,66 @@ class PCRLv2(nn.Module):
         masks = None if local else ue(self._seg, h, dt)
         return decoder_outputs, masks, middle_masks
 
+    # ---- PCRLv2.infer (engine extension): the eval-mode forward on the inference kernels ----
+    @staticmethod
+    def _unit_infer(u, x, dt, residual=None, act=None):
+        c, n = u.conv, u.bn_module
+        scale, shift = u._eval_coef.get(n)
+        return ops2d.conv2d_infer(x, c.weight, c.bias, scale, shift, u._packed, u.stride, u.pad, u.up, u.act if act is None else act, dt, residual=residual)
+
+    @torch.no_grad()
+    def infer(self, x, local=False, *, features_only=False, upsample=True):
+        """The values of `model.eval()(x, local)` -- in bf16 up to the roundings of the intermediate tensors this path does not store -- with every
+        Conv2d + BatchNorm2d (+ identity) + ReLU as ONE launch where the kernel family has the epilogue (ops2d.conv2d_infer), the stem's
+        normalisation + ReLU inside its max-pool, and the packed weights and eval-mode coefficients cached across calls.  Whatever
+        `self.training` says; no parameter, running statistic or counter of the model is touched (the engine-side caches -- packed weights, the stem's
+        pack, the eval-mode coefficients -- are filled on first use), no autograd graph is built.
+        -> ([(pro, pre) x 5], masks | None, [mask x 5]) as forward.  features_only: ([(pro, pre) x 5], None, []) -- no segmentation head, no
+        deep-supervision heads, no upsampling (the second view and the local views of train_2d.validate).  upsample=False hands the five
+        deep-supervision maps out at their OWN resolution (float32, H / 2^(4-i)): train_2d.validate interpolates inside its reduction."""
+        if not x.is_cuda:
+            raise RuntimeError("PCRLv2 (pcrlv2_amd) runs on the GPU only: input is on %s and there is no CPU fallback" % x.device)
+        dt, ui = self.compute_dtype, self._unit_infer
+        enc, stem = self.model.encoder, self.model.encoder._stem
+        x = x.float()
+        x = x if x.is_contiguous() else x.contiguous()
+        w0 = stem.conv.weight
+        if ops2d.stem_ok(x, w0, dt):          # the dedicated stem kernel on the float32 image (what the training step runs), statistics not wanted
+            if getattr(stem, "_packed_stem", None) is None:
+                stem._packed_stem = ops2d.PackedStem()
+            N, _, H, W = x.shape
+            y = ops2d.new_act2(N, H // 2, W // 2, 64, dt, x.device)
+            ops2d.lib().call("pcrl_stem7_fwd", x, stem._packed_stem.get(w0), y, None, N, H, W, ops2d.dtype_code(dt), ops2d.stream_handle())
+        else:
+            y = ops2d.conv2d_forward(ops2d.image_to_act(x, dt, 8), w0, None, stem._packed, stem.stride, stem.pad, 0, dt, want_stats=False)[0]
+        h = ops2d.bn_relu_maxpool_forward(y, *stem._eval_coef.get(stem.bn_module), dt)      # relu(bn1(.)) inside the pool: not stored at full resolution
+        for layer in (enc.layer1, enc.layer2, enc.layer3, enc.layer4):
+            for blk in layer:
+                idn = h if blk._ud is None else ui(blk._ud, h, dt)
+                h = ui(blk._u2, ui(blk._u1, h, dt), dt, residual=idn, act=ACT_RELU)        # relu(bn2(conv2(.)) + identity) in conv2's epilogue
+        decoder_outputs, middle_masks = [], []
+        for i, blk in enumerate(self.model.decoder.blocks):
+            h = ui(blk._u2, ui(blk._u1, h, dt), dt)
+            ph = blk.predictor_head
+            g = ops2d.gap_forward(h, dt)
+            C = g.shape[1]
+            x_pro = ops.bn_act_apply(g.contiguous(), *blk._eval_coef_bn.get(blk.bn), g.shape[0], C, ACT_NONE, torch.float32)
+            hid = ops.bn_act_apply(ops.linear_forward(x_pro, ph[0].weight, ph[0].bias).contiguous(), *blk._eval_coef_ph.get(ph[1]), g.shape[0], 2 * C,
+                                   ACT_RELU, torch.float32)
+            decoder_outputs.append((x_pro, ops.linear_forward(hid, ph[3].weight, ph[3].bias)))
+            if not features_only:
+                x_mask = self._unit_eval(blk._ud3, ui(blk._ud0, h, dt), dt)
+                # (reference quirk, kept as in _forward_eval: the maps are computed and upsampled for `local` too)
+                middle_masks.append(ops2d.bilinear_forward(ops2d.to_act2(x_mask, torch.float32), 2 ** (4 - i)) if upsample else x_mask)
+        if features_only:
+            return decoder_outputs, None, []
+        masks = None if local else self._unit_eval(self._seg, h, dt)
+        return decoder_outputs, masks, middle_masks
+
     def _begin_pass(self, x):
         if not x.is_cuda:
             raise RuntimeError("PCRLv2 (pcrlv2_amd) runs on the GPU only: input is on %s and there is no CPU fallback" % x.device)
+        ops2d.bump_stats_epoch()        # this forward moves running statistics: infer's cached eval-mode coefficients are stale
         pass_idx = ops.next_pass()
         for u in self._all_units():
             u._pass_idx = pass_idx

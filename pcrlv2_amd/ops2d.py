@@ -5,10 +5,12 @@ launches kernels of the C ABI (include/pcrl_hip.h, "2D path"); there is no eager
 """
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from . import config, ops
-from ._lib import ACT_RELU, PcrlError, dtype_code, lib, stream_handle
+from ._lib import ACT_NONE, ACT_RELU, PcrlError, dtype_code, lib, stream_handle
 
 
 def new_act2(N, H, W, C, dtype, device) -> torch.Tensor:
@@ -168,6 +170,133 @@ def conv2d_forward(x, w, bias, packed: PackedConv2d, stride, pad, up, dtype, wan
     L.call("pcrl_conv2d_fwd", x, wf, None if bias is None else bias.detach(), y, partial, rows, N, Hi, Wi, CiP, Co, KH, KW, stride, pad,
            int(up), int(out_f32), dtype_code(dtype), s)
     return y, partial, rows
+
+
+# ----------------------------------------------------------------------------------------------
+# inference forward (PCRLv2.infer): eval-mode BatchNorm2d (+ identity) + ReLU in the convolution's epilogue
+# ----------------------------------------------------------------------------------------------
+INFER_FUSED_2D = True      # module attribute (tools/val2d_forward_probe.py flips it): False = conv2d_infer always runs the separate passes
+_stats_epoch = 0
+
+
+def bump_stats_epoch():
+    """A training-mode forward is about to move BatchNorm running statistics through the library (no torch version counter sees that)."""
+    global _stats_epoch
+    _stats_epoch += 1
+
+
+class EvalCoef:
+    """ops.bn_eval_coef of one BatchNorm2d, cached until its parameters or running statistics change: the weights epoch (optimizer steps,
+    load_state_dict), the statistics epoch (training-mode forwards) and the tensors' own version counters (in-place edits by the caller).
+    The statistics epoch is bumped by PCRLv2._begin_pass, which every training-mode forward of the MODEL goes through (forward, forward_engine); a
+    training-mode call on a sub-module alone (model.model.encoder(x)) moves running statistics through the library without it -- call
+    ops2d.bump_stats_epoch() after such a call before the next infer."""
+
+    def __init__(self):
+        self.key, self.coef = None, None
+        self._guard = ops._CacheGuard()
+
+    def get(self, n):
+        ts = (n.weight, n.bias, n.running_mean, n.running_var)
+        key = (ops._weights_epoch, _stats_epoch) + tuple((t._version, t.data_ptr()) for t in ts)
+        if key != self.key:
+            self.coef = ops.bn_eval_coef(*ts)
+            self.key = key
+            self._guard._built(n.weight.device)
+        else:
+            self._guard._reading(n.weight.device)
+        return self.coef
+
+
+def infer_fused_route2d(N, Hi, Wi, CiP, Co, KH, KW, stride, pad, up, dtype, residual=False) -> bool:
+    """Host only: does conv2d_infer run this eval-mode Conv2d + BatchNorm2d (+ identity) + ReLU / no activation as ONE kernel?"""
+    if not INFER_FUSED_2D:
+        return False
+    return bool(lib().call("pcrl_conv2d_fwd_affine_fused", N, Hi, Wi, CiP, Co, KH, KW, stride, pad, int(up), int(bool(residual)), dtype_code(dtype)))
+
+
+def conv2d_infer(x, w, bias, scale, shift, packed: PackedConv2d, stride, pad, up, act, dtype, residual=None):
+    """Eval-mode Conv2d -> BatchNorm2d (scale, shift: ops.bn_eval_coef) -> (+ residual) -> act for inference: no autograd, nothing updated.
+    Where the kernel family has the epilogue (infer_fused_route2d) ONE launch -- the pre-normalisation tensor is neither written nor read back;
+    otherwise conv2d_forward + bn_act_apply (+ add_relu_forward), exactly the passes of PCRLv2._forward_eval.  `residual` (the BasicBlock's
+    identity, layout and dtype of the output) needs act = ReLU: the reference applies relu(bn2(conv2(.)) + identity)."""
+    N, Hi, Wi, CiP = dims2(x)
+    Co, Ci, KH, KW = w.shape
+    if CiP < Ci or x.dtype != dtype:
+        raise PcrlError(f"conv2d_infer: input has {CiP} channels in {x.dtype}, weight wants {Ci} in {dtype}")
+    if act not in (ACT_NONE, ACT_RELU) or (residual is not None and act != ACT_RELU):
+        raise PcrlError("conv2d_infer: ReLU or no activation; a residual needs ReLU")
+    geom = (N, Hi, Wi, CiP, Co, KH, KW, stride, pad, up, dtype)
+    if residual is not None and not infer_fused_route2d(*geom, residual=True) and infer_fused_route2d(*geom):
+        # the wide-brick epilogue has no residual operand: convolution + normalisation in one pass, the identity and the ReLU in the add pass
+        return add_relu_forward(conv2d_infer(x, w, bias, scale, shift, packed, stride, pad, up, ACT_NONE, dtype), residual, dtype)
+    if not infer_fused_route2d(*geom, residual=residual is not None):
+        y = conv2d_forward(x, w, bias, packed, stride, pad, up, dtype, want_stats=False)[0]
+        _, Ho, Wo, _ = dims2(y)
+        a = ops.bn_act_apply(y, scale, shift, N * Ho * Wo, Co, ACT_NONE if residual is not None else act, dtype)
+        return a if residual is None else add_relu_forward(a, residual, dtype)
+    wf, _ = packed.get(w, dtype, CiP)
+    Hl, Wl = (2 * Hi, 2 * Wi) if up else (Hi, Wi)
+    a = new_act2(N, out_size(Hl, KH, stride, pad), out_size(Wl, KW, stride, pad), Co, dtype, x.device)
+    if residual is not None and (residual.dtype != dtype or dims2(residual) != dims2(a)):
+        raise PcrlError("conv2d_infer: the residual must have the layout and dtype of the output")
+    lib().call("pcrl_conv2d_fwd_affine", x, wf, None if bias is None else bias.detach(), scale, shift, residual, a, N, Hi, Wi, CiP, Co, KH, KW,
+               stride, pad, int(up), act, dtype_code(dtype), stream_handle())
+    return a
+
+
+def bn_relu_maxpool_forward(y, scale, shift, dtype):
+    """relu(scale * y + shift) followed by MaxPool2d(3, 2, 1) in one pass (pcrl_bn_relu_maxpool2d_3s2_fwd): the stem's full-resolution activation
+    is not stored.  -> pooled activation"""
+    N, H, W, C = dims2(y)
+    Ho, Wo = out_size(H, 3, 2, 1), out_size(W, 3, 2, 1)
+    p = new_act2(N, Ho, Wo, C, dtype, y.device)
+    idx = torch.empty((N, Ho, Wo, C), dtype=torch.uint8, device=y.device)
+    lib().call("pcrl_bn_relu_maxpool2d_3s2_fwd", y, scale, shift, p, idx, N, H, W, C, dtype_code(dtype), stream_handle())
+    return p
+
+
+def val2d_metrics(out1, masks, gt, feats1, feats2, feats_loc, acc):
+    """One batch's 2D validation metrics added to `acc` (float64 [17] on the device: sixteen batch-size-weighted sums + the sample count;
+    pcrl_val2d_metrics).  out1: float32 [B,3,H,W] in NHWC memory; masks: the five deep-supervision maps at their OWN resolution (float32 NHWC
+    memory, H / 2^(4-k)); gt: float32 [B,3,H,W] contiguous; feats*: per scale (pro, pre) float32, the local views' rows concatenated view-major."""
+    L, s = lib(), stream_handle()
+    B, H, W, C3 = dims2(out1)
+    ns = len(masks)
+    if ns != 5 or len(feats1) != 5 or len(feats2) != 5 or len(feats_loc) != 5 or C3 != 3:
+        raise PcrlError("val2d_metrics: five scales and 3-channel maps expected")
+    if acc.dtype != torch.float64 or acc.numel() != 17 or not acc.is_contiguous():
+        raise PcrlError("val2d_metrics: acc must be 17 contiguous float64 values")
+    nlocal, rem = divmod(feats_loc[0][0].shape[0], B)
+    if rem or nlocal < 1:
+        raise PcrlError("val2d_metrics: nlocal * B local rows expected")
+    gt = _nchw_f32(gt, out1.device)
+    if tuple(gt.shape) != (B, 3, H, W) or out1.dtype != torch.float32:
+        raise PcrlError("val2d_metrics: out1 float32 and gt [B,3,H,W] expected")
+    keep, mp, fp, Cs = [gt], [], [], []
+    for k, m in enumerate(masks):
+        m = _nhwc_f32(m)
+        if dims2(m) != (B, H >> (4 - k), W >> (4 - k), 3):
+            raise PcrlError(f"val2d_metrics: map {k} has dims {dims2(m)}, expected {(B, H >> (4 - k), W >> (4 - k), 3)}")
+        keep.append(m)
+        mp.append(m.data_ptr())
+    for k in range(5):
+        C = feats1[k][0].shape[1]
+        Cs.append(C)
+        for t, rows in ((feats1[k][0], B), (feats1[k][1], B), (feats2[k][0], B), (feats2[k][1], B), (feats_loc[k][0], nlocal * B), (feats_loc[k][1], nlocal * B)):
+            t = t.detach()
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                t = t.float().contiguous()
+            if tuple(t.shape) != (rows, C):
+                raise PcrlError(f"val2d_metrics: feature of scale {k} has shape {tuple(t.shape)}, expected {(rows, C)}")
+            keep.append(t)
+            fp.append(t.data_ptr())
+    # host arrays of device pointers / channel counts: read by the call itself (they become kernel arguments), not by the device
+    mp_a, fp_a, C_a = (ctypes.c_void_p * 5)(*mp), (ctypes.c_void_p * 30)(*fp), (ctypes.c_int * 5)(*Cs)
+    nb = L.call("pcrl_val2d_metrics_ws_bytes", B, H, W, nlocal)
+    L.call("pcrl_val2d_metrics", out1, ctypes.addressof(mp_a), gt, ctypes.addressof(fp_a), ctypes.addressof(C_a), acc, ops.workspace(nb, out1.device), nb,
+           B, H, W, nlocal, 1e-8, s)
+    return acc
 
 
 def conv2d_backward(x, dy, w, packed: PackedConv2d, stride, pad, up, dtype, need_dx=True, below=None):

@@ -17,15 +17,18 @@ import sys
 import time
 
 import torch
+import torch.distributed as dist
 
 from . import config as _cfg
 from . import ddp as _ddp
 from . import functions as _fn
 from . import ops as _ops
+from . import ops2d as _ops2d
 from .functions2d import MaskMSEFn, SegMSEFn, mse_loss2d
 from .models.pcrlv2_model import PCRLv2
 from .optim import FusedSGD
 from .train_3d import BETA_PERIOD, COS_MAX_TERMS, CosineSimilarityMean, _fused_cos_losses, _to_gpu, cos_loss, seed_everything  # noqa: F401  (cos_loss: train_2d.py:111-117)
+from .train_3d import _val_shard, val_beta
 from .utils import AverageMeter, adjust_learning_rate
 
 
@@ -120,6 +123,69 @@ def train_step(model, optimizer, batch, epoch, criterion, cosine):
     return tuple(l.detach() for l in losses)
 
 
+NUM_SCALES = 5
+VAL_KEYS = (("mse_out",) + tuple("mse_mid%d" % k for k in range(NUM_SCALES)) + tuple("cos_global%d" % k for k in range(NUM_SCALES))
+            + tuple("cos_local%d" % k for k in range(NUM_SCALES)))
+
+
+def _mean_scales(m, name):
+    return sum(m[name + str(k)] for k in range(NUM_SCALES)) / NUM_SCALES
+
+
+def val_total(m, epoch):
+    """The expectation of the training loss (train_2d.py:139-168) over its uniform scale draws, from the sixteen per-scale means."""
+    return m["mse_out"] + _mean_scales(m, "cos_global") + _mean_scales(m, "cos_local") + val_beta(epoch) * _mean_scales(m, "mse_mid")
+
+
+def validate(model, loader, epoch, group=None):
+    """One pass over held-out data (the reference ships train_val_txt/chest_valid.txt and never reads it: data.py:59 hands the training loader out
+    as 'eval'): the terms of the training loss in eval mode at EVERY one of the five scale indices -- so no random number is drawn and the total is
+    the expectation of train_2d.py:139-168 over its draws, comparable to the training log.  Per batch: PCRLv2.infer on view 1 (maps at their own
+    resolution), on view 2 and on the concatenated local views (features only), then pcrl_val2d_metrics into a device accumulator; ONE host
+    synchronisation and read-back at the end (after ONE all_reduce of the seventeen sums when there is a process group of more than one rank).  The
+    loader's augmentation draws are reset to its seed first (`reset_rng()`): every pass sees the same data, two passes on the same weights give
+    bit-identical numbers.  `model.training` is not changed.
+    -> {'mse_out', 'mse_mid0..4', 'cos_global0..4', 'cos_local0..4', 'total', 'n'}; sample-weighted means (a ragged last batch counts by its size)."""
+    dev = next(model.parameters()).device
+    if hasattr(loader, "reset_rng"):
+        loader.reset_rng()
+    distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
+    acc = torch.zeros(len(VAL_KEYS) + 1, dtype=torch.float64, device=dev)
+    with torch.no_grad():
+        for batch in (_val_shard(loader, group) if distributed else loader):
+            view1, view2, target, _gt2, local_views = batch
+            view1, view2, target = _to_gpu(view1), _to_gpu(view2), _to_gpu(target)
+            feats1, out1, masks1 = model.infer(view1, upsample=False)
+            feats2, _, _ = model.infer(view2, features_only=True)
+            loc = _ops.concat_batch([_to_gpu(v) for v in local_views])
+            feats_loc, _, _ = model.infer(loc, local=True, features_only=True)
+            _ops2d.val2d_metrics(out1, masks1, target, feats1, feats2, feats_loc, acc)
+    if distributed:
+        dist.all_reduce(acc, group=group)
+    host = acc.cpu().tolist()          # the pass's one synchronisation
+    n = host[-1]
+    out = {k: (v / n if n else float("nan")) for k, v in zip(VAL_KEYS, host)}
+    out["total"] = val_total(out, epoch)
+    out["n"] = int(round(n))
+    return out
+
+
+def _best_checkpoint_name(args):
+    return os.path.join(args.output, "{}_{}_{}_{}_best.pt".format(args.model, args.n, args.phase, args.ratio))
+
+
+def save_if_best(args, model, optimizer, epoch, val, best):
+    """--save_best: the 2D checkpoint layout (train_2d.py:96-107: the ENCODER's state_dict) plus 'val' (validate's dict), written whenever `total`
+    improves strictly.  -> the best total so far."""
+    if best is not None and not val["total"] < best:
+        return best
+    if hasattr(model, "flush_counters"):
+        model.flush_counters()
+    torch.save({'opt': args, 'state_dict': model.model.encoder.state_dict(), 'optimizer': optimizer.state_dict(), 'epoch': epoch, 'val': dict(val)},
+               _best_checkpoint_name(args))
+    return val["total"]
+
+
 def train_pcrlv2(args, data_loader, out_channel=3):
     distributed = int(os.environ.get("WORLD_SIZE", "1")) > 1
     # a group this call creates is this call's to take down (see train_3d.train_pcrlv2_3d)
@@ -164,6 +230,7 @@ def _train_pcrlv2(args, data_loader, distributed):
     if getattr(args, "resume", None):
         if chatty:
             print("==> resumed the ENCODER from {} (the 2D checkpoint layout holds nothing else); continuing with epoch {}".format(args.resume, first_epoch))
+    val_every, best_total = int(getattr(args, "val_every", 0) or 0), None
     for epoch in range(first_epoch, args.epochs + 1):
         adjust_learning_rate(epoch, args, optimizer)
         if chatty:
@@ -177,6 +244,14 @@ def _train_pcrlv2(args, data_loader, distributed):
                 model.flush_counters()
                 state = {'opt': args, 'state_dict': model.model.encoder.state_dict(), 'optimizer': optimizer.state_dict(), 'epoch': epoch}
                 torch.save(state, os.path.join(args.output, "{}_{}_{}_{}_{}.pt".format(args.model, args.n, args.phase, args.ratio, epoch)))
+        if val_every > 0 and (epoch + 1) % val_every == 0:      # --val_every N: held-out metrics after every N-th epoch (0: never -- the reference)
+            val = validate(model, data_loader['eval'], epoch)
+            if chatty:
+                print('Val: [{0}]\ttotal {1:.4f}\tmg {2:.4f}\tcos {3:.4f}\tlocal {4:.4f}\tmid {5:.4f}\t({6} samples)'.format(
+                    epoch, val["total"], val["mse_out"], _mean_scales(val, "cos_global"), _mean_scales(val, "cos_local"), _mean_scales(val, "mse_mid"), val["n"]))
+                sys.stdout.flush()
+                if getattr(args, "save_best", False):
+                    best_total = save_if_best(args, model, optimizer, epoch, val, best_total)
         if _cfg.EMPTY_CACHE_PER_EPOCH:           # the reference's per-epoch empty_cache (train_3d.py:83 / train_2d.py:108); the steady-state pools are kept (ops.empty_cache)
             torch.cuda.empty_cache() if _cfg.EMPTY_CACHE_RAW else _ops.empty_cache()
     return model
