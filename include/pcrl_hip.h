@@ -709,6 +709,27 @@ int pcrl_nchw_to_nhwc_pad(const float* x, void* out, int N, int C, int64_t HW, i
  * operand) and through the predictor head (pcrlv2_model.py:125-127, pcrlv2_model_3d.py:69-70) -- autograd's aten::add on a [N, C] matrix */
 int pcrl_add_f32(const float* a, const float* b, float* out, int64_t n, pcrl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * 2D path, supervised fine-tuning (csrc/cls_head.hip, csrc/auroc.hip).
+ * pcrl_cls_head_fwd / _bwd -- smp's ClassificationHead(pooling='avg', dropout=p, activation='sigmoid') on the encoder's last feature map and
+ *   nn.BCELoss on its output, as one operator (aten::mean + aten::native_dropout + aten::addmm + aten::sigmoid + aten::binary_cross_entropy and
+ *   their backwards).  a: `dtype` NHWC [N][H][W][C] (C a power of two, 32..512); keep: uint8 [N][C] dropout keep mask, NULL = no dropout (eval);
+ *   keep_scale = 1 / (1 - p); w float32 [K][C], b float32 [K] (K <= 64); labels uint8 [N][K] (non-zero = positive) or NULL.
+ *   forward : probs float32 [N][K]; pooled float32 [N][C] (the mean over H*W, BEFORE the mask -- saved for the backward); with labels,
+ *             loss[0] = mean over N*K of max(z,0) - y z + log1p(exp(-|z|)) on the logit z (= BCELoss(sigmoid(z), y) wherever that does not clamp
+ *             its logarithm), float64 partial per sample + a fixed-order second launch: deterministic.  labels and loss are both NULL or both
+ *             given.  ws: pcrl_cls_head_ws_bytes(N), only with labels.  The activation is read once.
+ *   backward: from dloss[0] -- da `dtype` [N][H][W][C] (written once; NULL: not wanted), dw float32 [K][C], db float32 [K].  The activation is
+ *             not read.  Two launches, no atomics.
+ * pcrl_auroc_counts -- per class k of probs float32 [M][K] / labels uint8 [M][K]: counts[k] = {2 #(pos > neg) + #(pos == neg), #pos, #neg} (int64
+ *   [K][3]) over all (positive, negative) pairs; exact integer counting, float comparison.  AUROC_k = counts[k][0] / (2 P Q) (host). */
+size_t pcrl_cls_head_ws_bytes(int N);
+int pcrl_cls_head_fwd(const void* a, const uint8_t* keep, float keep_scale, const float* w, const float* b, const uint8_t* labels, float* probs,
+                      float* pooled, float* loss, void* ws, size_t ws_bytes, int N, int H, int W, int C, int K, int dtype, pcrl_stream_t stream);
+int pcrl_cls_head_bwd(const float* probs, const uint8_t* labels, const float* dloss, const float* pooled, const uint8_t* keep, float keep_scale,
+                      const float* w, void* da, float* dw, float* db, int N, int H, int W, int C, int K, int dtype, pcrl_stream_t stream);
+int pcrl_auroc_counts(const float* probs, const uint8_t* labels, int64_t* counts, int64_t M, int K, pcrl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

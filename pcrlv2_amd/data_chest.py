@@ -377,3 +377,242 @@ def chest_pretask_loaders(args, device=None):
         return ev
 
     return _LazyLoaders(train, make_eval)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Supervised fine-tuning: the labelled lists, the labelled slot loader, the training and the evaluation transform
+# ---------------------------------------------------------------------------------------------------------------
+MAX_CLASSES = 31           # the labels of a sample travel through the slots as one non-negative int32 bitmask
+
+
+def chest_labelled_list(data_dir: str, list_file: str):
+    """utils.get_chest_list (utils.py:7-19): the `name l0 ... l(K-1)` lines of `list_file` -> (names joined to `data_dir`, labels uint8 [n, K]).
+    Every line must carry the same number K <= 31 of 0/1 labels; a missing list is an error."""
+    if not os.path.exists(list_file):
+        raise SystemExit(f"the labelled image list {list_file} does not exist")
+    names, rows = [], []
+    with open(list_file) as f:
+        for ln, line in enumerate(f, start=1):
+            items = line.split()
+            if not items:
+                continue
+            try:
+                lab = [int(v) for v in items[1:]]
+            except ValueError:
+                raise ValueError(f"{list_file}:{ln}: labels must be integers") from None
+            if any(v not in (0, 1) for v in lab):
+                raise ValueError(f"{list_file}:{ln}: labels must be 0 or 1")
+            if rows and len(lab) != len(rows[0]):
+                raise ValueError(f"{list_file}:{ln}: {len(lab)} labels where the lines before have {len(rows[0])}")
+            names.append(os.path.join(data_dir, items[0]))
+            rows.append(lab)
+    K = len(rows[0]) if rows else 0
+    if rows and not 1 <= K <= MAX_CLASSES:
+        raise ValueError(f"{list_file}: {K} labels per line; 1..{MAX_CLASSES} are supported")
+    return names, np.asarray(rows, dtype=np.uint8).reshape(len(rows), K)
+
+
+def pack_labels(labels) -> np.ndarray:
+    """uint8 [n, K] (K <= 31) -> int32 [n] bitmasks, bit k = label k."""
+    labels = np.asarray(labels, dtype=np.uint8)
+    n, K = labels.shape
+    if K > MAX_CLASSES:
+        raise ValueError(f"{K} labels do not fit the int32 bitmask ({MAX_CLASSES} at most)")
+    return ((labels != 0).astype(np.int64) << np.arange(K, dtype=np.int64)).sum(axis=1).astype(np.int32)
+
+
+def unpack_labels(masks, K: int) -> np.ndarray:
+    """int32 [n] bitmasks -> uint8 [n, K]."""
+    masks = np.asarray(masks, dtype=np.int64).reshape(-1, 1)
+    return ((masks >> np.arange(K, dtype=np.int64)) & 1).astype(np.uint8)
+
+
+def chest_finetune_split(data_dir: str, ratio: float, list_file: str = "train_val_txt/chest_train.txt"):
+    """The supervised training set: the LAST 1 - ratio of the training list, `names[int(len * ratio):]` (utils.get_luna_finetune_list's rule; the README:
+    "top K% images for pre-training and last (100-K)% for fine-tuning") -- the complement of chest_file_list's.  -> (names, labels uint8 [n, K])"""
+    names, labels = chest_labelled_list(data_dir, list_file)
+    cut = int(len(names) * ratio)
+    names, labels = names[cut:], labels[cut:]
+    if not names:
+        raise SystemExit(f"--ratio {ratio} leaves no image of {list_file} for fine-tuning (the last 1 - ratio of the list is the supervised training set); "
+                         "lower --ratio")
+    return names, labels
+
+
+def eval_records(dims, S=GLOBAL_SIZE):
+    """The view records of the EVALUATION transform Resize((S, S)) (bilinear) -> ToTensor -> Normalize, expressed for the pre-task's two spatial
+    kernels: the crop is the whole image, the rotation is the angle-0 identity, no flip.  dims: [B, >=3] (H, W, C) -> int64 [B, NPARAM] (offsets left 0)."""
+    dims = np.asarray(dims, np.int64)
+    rec = np.zeros((dims.shape[0], NPARAM), np.int64)
+    rec[:, P_H], rec[:, P_W], rec[:, P_C] = dims[:, 0], dims[:, 1], dims[:, 2]
+    rec[:, P_CW], rec[:, P_CH] = dims[:, 1], dims[:, 0]
+    rec[:, P_A0:P_A5 + 1] = rotate_fixed(0.0, S, S)
+    return rec
+
+
+def apply_spatial(src, rec_dev, rec_host, S):
+    """The two spatial kernels alone (no photometric launch) over one group of views: -> (view uint8 [V,3,S,S] (plane 0 only for a one-plane source),
+    Normalize(ToTensor(view)) float32 [V,3,S,S])."""
+    V = rec_host.shape[0]
+    dev = src.device
+    inter = torch.empty(int((rec_host[:, P_CH].astype(np.int64) * S * rec_host[:, P_C]).sum()), dtype=torch.uint8, device=dev)
+    _call("pcrl_aug2d_hresample", src, rec_dev, inter, V, S, int(rec_host[:, P_CH].max()))
+    view = torch.empty((V, 3, S, S), dtype=torch.uint8, device=dev)
+    target = torch.empty((V, 3, S, S), dtype=torch.float32, device=dev)
+    _call("pcrl_aug2d_spatial", inter, rec_dev, view, target, V, S)
+    return view, target
+
+
+class GpuChestLabelledAugment(GpuChestAugment):
+    """__call__(pixels [B, cap] uint8, record [B, 4] int32 (H, W, C, label bitmask) on the host) -> (x [B,3,224,224] float32, y [B,K] uint8 on the device).
+    train: RandomResizedCrop(224, scale (0.3, 1)) -> RandomRotation(10) -> RandomHorizontalFlip -> ToTensor -> Normalize -- the pre-task's un-jittered
+    target; eval: Resize((224, 224)) -> ToTensor -> Normalize (eval_records).  Two launches either way."""
+
+    def __init__(self, device, seed, n_class, train):
+        super().__init__(device, seed)
+        self.n_class, self.train = int(n_class), bool(train)
+
+    def records(self, dims):
+        dims = np.asarray(dims, np.int64)
+        H, W, C = dims[:, 0], dims[:, 1], dims[:, 2]
+        sizes = H * W * C
+        offs = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+        rec = draw_views(self.rng, H, W, C, GLOBAL_SIZE, GLOBAL_SCALE, cutout=False) if self.train else eval_records(dims)
+        pack_offsets(rec, offs, np.arange(dims.shape[0]), GLOBAL_SIZE)
+        return rec, offs, sizes
+
+    @torch.no_grad()
+    def __call__(self, pixels, record):
+        rec4 = record.numpy() if torch.is_tensor(record) else np.asarray(record)
+        B = rec4.shape[0]
+        rec, offs, sizes = self.records(rec4[:, :3])
+        both = np.concatenate([rec.astype(np.int32).reshape(-1), unpack_labels(rec4[:, 3], self.n_class).astype(np.int32).reshape(-1)])
+        host = torch.from_numpy(both)
+        if self.device.type == "cuda":
+            host = host.pin_memory()
+        dev = host.to(self.device, non_blocking=True)          # the records and the labels in one host-to-device copy
+        rec_d, y = dev[:rec.size].view(B, NPARAM), dev[rec.size:].view(B, self.n_class).to(torch.uint8)
+        src = torch.empty(int(sizes.sum()), dtype=torch.uint8, device=self.device)
+        if torch.is_tensor(pixels) and pixels.dim() == 2 and B > 0 and bool((sizes == pixels.shape[1]).all()):
+            src.view(B, -1).copy_(pixels, non_blocking=True)
+        else:
+            for n in range(B):
+                src[int(offs[n]):int(offs[n] + sizes[n])].copy_(pixels[n, :int(sizes[n])], non_blocking=True)
+        _view, x = apply_spatial(src, rec_d, rec, GLOBAL_SIZE)
+        return x, y
+
+
+class LabelledImages(ChestImages):
+    """ChestImages over (path, label bitmask) entries: (pixels [cap] uint8, (H, W, C, bitmask) int32)."""
+
+    def __init__(self, entries, cap):
+        super().__init__([e[0] for e in entries], cap)
+        self.masks = [int(e[1]) for e in entries]
+
+    def __getitem__(self, i):
+        pix, dims = super().__getitem__(i)
+        return pix, torch.cat([dims, torch.tensor([self.masks[i]], dtype=torch.int32)])
+
+
+class _SlotLabelledImages(_SlotImages):
+    """_SlotImages over (path, label bitmask) entries: the slot's int32 record is (H, W, C, bitmask)."""
+
+    def __init__(self, entries, pix_buf, rec_buf):
+        super().__init__([e[0] for e in entries], pix_buf, rec_buf)
+        self.masks = [int(e[1]) for e in entries]
+
+    def __getitem__(self, key):
+        slot, row, i = key
+        a = decode(self.files[i])
+        if a.size > self.cap:
+            raise ValueError(f"{self.files[i]}: {a.shape} does not fit the {self.cap}-byte image slots (sized from the first file)")
+        self.pix[slot, row, :a.size] = torch.from_numpy(a.reshape(-1))
+        self.dims[slot, row] = torch.tensor(tuple(a.shape) + (self.masks[i],), dtype=torch.int32)
+        return slot, row
+
+
+class ChestLabelledKind(ChestKind):
+    """ChestKind whose samples carry their labels through AugmentedLoader's slots as they are: the loader's `files` are (path, label bitmask) entries
+    (labelled_entries), the host-side per-sample record is (H, W, C, bitmask) int32 [4], and the augment object unpacks it."""
+
+    def __init__(self, entries, n_class, train):
+        super().__init__([e[0] for e in entries])
+        self.n_class, self.train = int(n_class), bool(train)
+
+    def slot_shapes(self):
+        return [((self.cap,), torch.uint8), ((4,), torch.int32)]
+
+    def slot_dataset(self, files, bufs):
+        return _SlotLabelledImages(files, *bufs)
+
+    def dataset(self, files):
+        return LabelledImages(files, self.cap)
+
+    def augment(self, device, seed):
+        return GpuChestLabelledAugment(device, seed, self.n_class, self.train)
+
+
+def labelled_entries(names, labels):
+    return list(zip(names, pack_labels(labels).tolist()))
+
+
+class _LazyBuilt(dict):
+    """A dict of loaders whose entries are built -- worker processes, shared batch slots, list files read -- when first asked for."""
+
+    def __init__(self, ready, makers):
+        super().__init__(ready)
+        self._makers = dict(makers)
+        for k in makers:
+            super().__setitem__(k, None)
+
+    def __getitem__(self, key):
+        make = self._makers.pop(key, None)
+        if make is not None:
+            super().__setitem__(key, make())
+        return super().__getitem__(key)
+
+    def get(self, key, default=None):
+        return self[key] if key in self else default
+
+
+def chest_finetune_loaders(args, device=None):
+    """{'train', 'eval', 'test'} for --phase finetune / scratch: the last 1 - ratio of ./train_val_txt/chest_train.txt with the training transform (shuffled;
+    one equal shard per rank), --val_list and --test_list with the evaluation transform (this rank's contiguous shard, unshuffled; built -- and their
+    list files read -- on first use).  Every loader yields (x [B,3,224,224] float32, y [B,K] uint8) on the device."""
+    device = device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu")
+    K = int(getattr(args, "n_class", 14))
+    names, labels = chest_finetune_split(args.data, args.ratio)
+    if labels.shape[1] != K:
+        raise SystemExit(f"./train_val_txt/chest_train.txt carries {labels.shape[1]} labels per line, --n_class is {K}")
+    missing = [p for p in names if not os.path.isfile(p)]
+    if missing:
+        raise FileNotFoundError(f"{len(missing)} file(s) of train_val_txt/chest_train.txt are not in {args.data}, e.g. {missing[0]}")
+    print(f"total fine-tuning images {len(names)}")
+    rank = int(os.environ.get("RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    seed = getattr(args, "seed", 0)
+    entries = labelled_entries(names, labels)
+    if world > 1:
+        entries = entries[:len(entries) - len(entries) % world]
+    train = AugmentedLoader(entries[rank::world], args.b, args.workers, device, True, seed + rank, drop_last=world > 1, kind=ChestLabelledKind(entries, K, True))
+
+    def held_out(list_file, flag):
+        def make():
+            if not os.path.exists(list_file):
+                raise SystemExit(f"the labelled image list {list_file} ({flag}) does not exist")
+            n, lab = chest_labelled_list(args.data, list_file)
+            if not n:
+                raise SystemExit(f"the labelled image list {list_file} ({flag}) is empty")
+            if lab.shape[1] != K:
+                raise SystemExit(f"{list_file} carries {lab.shape[1]} labels per line, --n_class is {K}")
+            gone = [p for p in n if not os.path.isfile(p)]
+            if gone:
+                raise FileNotFoundError(f"{len(gone)} file(s) of {list_file} are not in {args.data}, e.g. {gone[0]}")
+            part = eval_shard(labelled_entries(n, lab), rank, world)
+            ev = AugmentedLoader(part, args.b, args.workers, device, False, seed, kind=ChestLabelledKind(part or labelled_entries(n, lab), K, False))
+            ev.sharded = True
+            return ev
+        return make
+
+    return _LazyBuilt({"train": train}, {"eval": held_out(getattr(args, "val_list", "./train_val_txt/chest_valid.txt"), "--val_list"),
+                                         "test": held_out(getattr(args, "test_list", "./train_val_txt/chest_test.txt"), "--test_list")})

@@ -489,6 +489,39 @@ class MaskMSEFn(Function):
         return d, None, None
 
 
+class ClsHeadFn(Function):
+    """BCELoss(classification_head(a), labels) -- smp's ClassificationHead(pooling='avg', dropout=p, activation='sigmoid') on the encoder's last
+    feature map (the reference's README, "Load the Encoder Part of a 2D Model") and the multi-label loss -- as ONE node on pcrl_cls_head_fwd / _bwd:
+    the activation is read once forward and not at all backward.  keep: uint8 [N,C] dropout keep mask (None: no dropout).
+    -> (loss 0-d float32, probs float32 [N,K]); the probabilities carry no gradient (they are the step's by-product for logging / metrics)."""
+
+    @staticmethod
+    def forward(ctx, a, w, b, labels, keep, p, mod):
+        dt = mod.compute_dtype
+        probs, pooled, loss = ops2d.cls_head_forward(a, w, b, dt, keep=keep, p=p, labels=labels)
+        ctx.like, ctx.dt, ctx.p = a, dt, p          # an INPUT held for its shape (the encoder node keeps it alive anyway); never read
+        ctx.aux = (labels, keep, pooled)
+        ctx.plist = (w, b)
+        ctx.pass_idx = getattr(mod, "_pass_idx", 1)
+        ctx.save_for_backward(probs)                # an OUTPUT needed in backward: never stashed on ctx directly (reference cycle)
+        ctx.mark_non_differentiable(probs)
+        ctx.set_materialize_grads(False)
+        return loss, probs
+
+    @staticmethod
+    def backward(ctx, dloss, _dprobs):
+        if dloss is None:
+            return (None,) * 7
+        w, b = ctx.plist
+        labels, keep, pooled = ctx.aux
+        (probs,) = ctx.saved_tensors
+        da, dw, db = ops2d.cls_head_backward(probs, labels, dloss, pooled, w, ctx.like, ctx.dt, keep=keep, p=ctx.p, need_da=ctx.needs_input_grad[0])
+        out = da, _park(w, dw), _park(b, db), None, None, None, None
+        mark_final(ctx, ctx.plist)
+        ctx.like = ctx.aux = None
+        return out
+
+
 def mse_loss2d(p, gt):
     """nn.MSELoss()(p, gt) for an NHWC-memory prediction [N,C,H,W] and a target in any layout (train_2d.py:165,167)."""
     from .functions import MSELossFn

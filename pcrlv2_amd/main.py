@@ -11,6 +11,8 @@ generated batches of the reference's shapes (no dataset on disk needed); a LUNA 
 (crops from disk, the reference's torchio augmentations restated on the GPU -- parity with torchio unpinned); with `--d 2` an image
 directory is read by pcrlv2_amd/data_chest.py (PNGs decoded by the workers, the reference's torchvision chain restated on the GPU at
 Pillow's arithmetic; the list is ./train_val_txt/chest_train.txt when it exists, otherwise every *.png under --data).
+`--d 2 --phase finetune --encoder_weights CKPT` (or `--phase scratch`) trains the 14-label chest classifier of the reference's README on the LAST
+1 - ratio of the training list (pcrlv2_amd/train_finetune.py); every other combination of --d / --phase exits with a message.
 """
 import argparse
 import os
@@ -50,6 +52,10 @@ _FLAGS = (
     ("val_list", "./train_val_txt/chest_valid.txt", str, "only with --d 2 and --val_every > 0: the held-out image list (`name label...` lines, names relative to --data); "
                                                         "a missing list is an error -- the held-out set is never carved out of the training list"),
     ("size2d", 224, int, "only with --d 2 --data synthetic: side of the global views (locals are 96x96)"),
+    ("test_list", "./train_val_txt/chest_test.txt", str, "only with --d 2 --phase finetune | scratch: the labelled list evaluated once after the last epoch "
+                                                        "(a missing list is an error when it is used)"),
+    ("n_class", 14, int, "only with --d 2 --phase finetune | scratch: labels per image (<= 31)"),
+    ("dropout", 0.2, float, "only with --d 2 --phase finetune | scratch: dropout in front of the classifier's linear layer"),
 )
 
 
@@ -115,9 +121,56 @@ class SyntheticChestLoader(SyntheticLunaLoader):
             yield x1, x2, gt, gt, loc
 
 
+class SyntheticLabelledChestLoader(SyntheticLunaLoader):
+    """Labelled 2D batches for --phase finetune | scratch: (x [b,3,S,S] float32, y [b,K] uint8).  The labels are a FIXED function of the image --
+    label k = (mean of channel k % 3 over cell k of a g x g grid, g = ceil(sqrt(K)), is positive) -- and the generator plants a random +-1 offset in
+    every cell under the noise, so the function is learnable and both label values occur for every class."""
+
+    def __init__(self, b, steps, size, n_class, seed=0, device=None):
+        super().__init__(b, steps, seed, device)
+        self.size, self.n_class = size, n_class
+        self.sharded = True                        # one stream per rank: nothing to cut
+
+    @staticmethod
+    def labels_of(x, n_class):
+        import math
+        import torch
+        g = int(math.ceil(math.sqrt(n_class)))
+        S = x.shape[-1]
+        c = S // g
+        cols = [x[:, k % 3, (k // g) * c:(k // g + 1) * c, (k % g) * c:(k % g + 1) * c].mean(dim=(1, 2)) > 0 for k in range(n_class)]
+        return torch.stack(cols, dim=1).to(torch.uint8)
+
+    def __iter__(self):
+        import math
+        import torch
+        kw = dict(generator=self.g, device=self.device)
+        g = int(math.ceil(math.sqrt(self.n_class)))
+        c = self.size // g
+        for _ in range(self.steps):
+            x = 0.5 * torch.randn(self.b, 3, self.size, self.size, **kw)
+            sign = (torch.rand(self.b, 3, g, g, **kw) < 0.5).float() * 2 - 1
+            x[:, :, :g * c, :g * c] += sign.repeat_interleave(c, dim=2).repeat_interleave(c, dim=3)
+            yield x, self.labels_of(x, self.n_class)
+
+
+def supervised(args):
+    return args.phase in ("finetune", "scratch")
+
+
 def get_dataloader(args):
     """`DataGenerator(args).pcrlv2_luna_pretask()` / `.pcrlv2_chest_pretask()` of the reference (data.py:63-99 / 14-61) -- `--data synthetic`:
-    generated batches."""
+    generated batches.  --d 2 --phase finetune | scratch: the labelled loaders {'train', 'eval', 'test'}."""
+    if args.d == 2 and supervised(args):
+        if args.data == 'synthetic':
+            rank = int(os.environ.get("RANK", "0"))
+            mk = lambda off: SyntheticLabelledChestLoader(args.b, args.steps_per_epoch, args.size2d, args.n_class, args.seed + off + rank)   # noqa: E731
+            return {'train': mk(0), 'eval': mk(7919), 'test': mk(15485)}
+        if os.path.isdir(args.data):
+            from .data_chest import chest_finetune_loaders
+            return chest_finetune_loaders(args)
+        raise SystemExit("--d 2 --phase {} needs --data synthetic or a directory of chest X-ray images listed, with their labels, in "
+                         "./train_val_txt/chest_train.txt".format(args.phase))
     if args.data == 'synthetic' and args.d == 2:
         rank = int(os.environ.get("RANK", "0"))
         ev = None
@@ -141,8 +194,26 @@ def get_dataloader(args):
                      "or every *.png under it)")
 
 
+def check_route(args):
+    """Every (model, d, phase) combination either has a training loop or ends here with a message: no parsed flag silently does nothing."""
+    if args.model != 'pcrlv2':
+        raise SystemExit("--model {}: only 'pcrlv2' is implemented".format(args.model))
+    if args.d not in (2, 3):
+        raise SystemExit("--d {}: 2 or 3".format(args.d))
+    if args.phase not in ('pretask', 'finetune', 'scratch'):
+        raise SystemExit("--phase {}: pretask, finetune or scratch".format(args.phase))
+    if args.d == 3 and args.phase != 'pretask':
+        raise SystemExit("--d 3 --phase {}: 3D fine-tuning is not implemented; supervised training exists for --d 2 (chest X-ray labels) only".format(args.phase))
+    if args.d == 2 and args.phase == 'finetune' and not args.encoder_weights:
+        raise SystemExit("--phase finetune needs --encoder_weights (a 2D pre-training checkpoint or a ResNet-18 state_dict); to train the classifier from "
+                         "random weights use --phase scratch")
+    if args.d == 2 and supervised(args) and not 1 <= args.n_class <= 31:
+        raise SystemExit("--n_class {}: 1..31".format(args.n_class))
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    check_route(args)
     os.makedirs(args.output, exist_ok=True)
     ids = [g for g in args.gpus.split(',') if g != '']
     if len(ids) > 1 and "WORLD_SIZE" not in os.environ:
@@ -161,6 +232,11 @@ def main(argv=None):
     elif args.model == 'pcrlv2' and args.phase == 'pretask' and args.d == 2:
         from .train_2d import train_pcrlv2
         train_pcrlv2(args, data_loader)
+    elif args.model == 'pcrlv2' and supervised(args) and args.d == 2:
+        from .train_finetune import train_chest_classifier
+        train_chest_classifier(args, data_loader)
+    else:       # check_route lets nothing else through; a combination added there without a loop must not fall through silently
+        raise SystemExit("no training loop for --model {} --d {} --phase {}".format(args.model, args.d, args.phase))
 
 
 if __name__ == '__main__':

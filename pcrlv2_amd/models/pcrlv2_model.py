@@ -270,6 +270,51 @@ class _SegmentationModel(nn.Module):
             self.encoder.load_state_dict(sd)
 
 
+def encoder_eval(enc, x, dt):
+    """ResNetEncoder in eval mode down to layer4's output, one pass per layer of the module chain (the encoder half of PCRLv2._forward_eval, shared
+    with ChestClassifier.forward in eval mode): convolution, BatchNorm2d on the running statistics, add + ReLU as separate launches."""
+    ue = PCRLv2._unit_eval
+    h = ue(enc._stem, ops2d.image_to_act(x.float(), dt, 8), dt)
+    h = ops2d.maxpool_forward(h, dt)[0]
+    for layer in (enc.layer1, enc.layer2, enc.layer3, enc.layer4):
+        for blk in layer:
+            t = ue(blk._u2, ue(blk._u1, h, dt), dt)
+            idn = h if blk._ud is None else ue(blk._ud, h, dt)
+            h = ops2d.add_relu_forward(t, ops2d.to_act2(idn, dt), dt)
+    return h
+
+
+def _unit_infer(u, x, dt, residual=None, act=None):
+    """One eval-mode Conv2d + BatchNorm2d (+ identity) + activation unit on the inference kernels (ops2d.conv2d_infer), coefficients cached."""
+    c, n = u.conv, u.bn_module
+    scale, shift = u._eval_coef.get(n)
+    return ops2d.conv2d_infer(x, c.weight, c.bias, scale, shift, u._packed, u.stride, u.pad, u.up, u.act if act is None else act, dt, residual=residual)
+
+
+def encoder_infer(enc, x, dt):
+    """ResNetEncoder in eval mode down to layer4's output on the inference kernels -- the encoder half of PCRLv2.infer, shared with
+    ChestClassifier.infer: the dedicated stem kernel on the float32 image where it applies, the stem's normalisation + ReLU inside its max-pool,
+    relu(bn2(conv2(.)) + identity) in conv2's epilogue.  No parameter, running statistic or counter is touched."""
+    ui, stem = _unit_infer, enc._stem
+    x = x.float()
+    x = x if x.is_contiguous() else x.contiguous()
+    w0 = stem.conv.weight
+    if ops2d.stem_ok(x, w0, dt):          # the dedicated stem kernel on the float32 image (what the training step runs), statistics not wanted
+        if getattr(stem, "_packed_stem", None) is None:
+            stem._packed_stem = ops2d.PackedStem()
+        N, _, H, W = x.shape
+        y = ops2d.new_act2(N, H // 2, W // 2, 64, dt, x.device)
+        ops2d.lib().call("pcrl_stem7_fwd", x, stem._packed_stem.get(w0), y, None, N, H, W, ops2d.dtype_code(dt), ops2d.stream_handle())
+    else:
+        y = ops2d.conv2d_forward(ops2d.image_to_act(x, dt, 8), w0, None, stem._packed, stem.stride, stem.pad, 0, dt, want_stats=False)[0]
+    h = ops2d.bn_relu_maxpool_forward(y, *stem._eval_coef.get(stem.bn_module), dt)      # relu(bn1(.)) inside the pool: not stored at full resolution
+    for layer in (enc.layer1, enc.layer2, enc.layer3, enc.layer4):
+        for blk in layer:
+            idn = h if blk._ud is None else ui(blk._ud, h, dt)
+            h = ui(blk._u2, ui(blk._u1, h, dt), dt, residual=idn, act=ACT_RELU)        # relu(bn2(conv2(.)) + identity) in conv2's epilogue
+    return h
+
+
 class PCRLv2(nn.Module):
     """reference pcrlv2_model.py:197-209"""
 
@@ -333,14 +378,7 @@ class PCRLv2(nn.Module):
         if not x.is_cuda:
             raise RuntimeError("PCRLv2 (pcrlv2_amd) runs on the GPU only: input is on %s and there is no CPU fallback" % x.device)
         dt, ue = self.compute_dtype, self._unit_eval
-        enc = self.model.encoder
-        h = ue(enc._stem, ops2d.image_to_act(x.float(), dt, 8), dt)
-        h = ops2d.maxpool_forward(h, dt)[0]
-        for layer in (enc.layer1, enc.layer2, enc.layer3, enc.layer4):
-            for blk in layer:
-                t = ue(blk._u2, ue(blk._u1, h, dt), dt)
-                idn = h if blk._ud is None else ue(blk._ud, h, dt)
-                h = ops2d.add_relu_forward(t, ops2d.to_act2(idn, dt), dt)
+        h = encoder_eval(self.model.encoder, x, dt)
         decoder_outputs, middle_masks = [], []
         for i, blk in enumerate(self.model.decoder.blocks):
             h = ue(blk._u2, ue(blk._u1, h, dt), dt)
@@ -357,12 +395,6 @@ class PCRLv2(nn.Module):
         return decoder_outputs, masks, middle_masks
 
     # ---- PCRLv2.infer (engine extension): the eval-mode forward on the inference kernels ----
-    @staticmethod
-    def _unit_infer(u, x, dt, residual=None, act=None):
-        c, n = u.conv, u.bn_module
-        scale, shift = u._eval_coef.get(n)
-        return ops2d.conv2d_infer(x, c.weight, c.bias, scale, shift, u._packed, u.stride, u.pad, u.up, u.act if act is None else act, dt, residual=residual)
-
     @torch.no_grad()
     def infer(self, x, local=False, *, features_only=False, upsample=True):
         """The values of `model.eval()(x, local)` -- in bf16 up to the roundings of the intermediate tensors this path does not store -- with every
@@ -375,24 +407,8 @@ class PCRLv2(nn.Module):
         deep-supervision maps out at their OWN resolution (float32, H / 2^(4-i)): train_2d.validate interpolates inside its reduction."""
         if not x.is_cuda:
             raise RuntimeError("PCRLv2 (pcrlv2_amd) runs on the GPU only: input is on %s and there is no CPU fallback" % x.device)
-        dt, ui = self.compute_dtype, self._unit_infer
-        enc, stem = self.model.encoder, self.model.encoder._stem
-        x = x.float()
-        x = x if x.is_contiguous() else x.contiguous()
-        w0 = stem.conv.weight
-        if ops2d.stem_ok(x, w0, dt):          # the dedicated stem kernel on the float32 image (what the training step runs), statistics not wanted
-            if getattr(stem, "_packed_stem", None) is None:
-                stem._packed_stem = ops2d.PackedStem()
-            N, _, H, W = x.shape
-            y = ops2d.new_act2(N, H // 2, W // 2, 64, dt, x.device)
-            ops2d.lib().call("pcrl_stem7_fwd", x, stem._packed_stem.get(w0), y, None, N, H, W, ops2d.dtype_code(dt), ops2d.stream_handle())
-        else:
-            y = ops2d.conv2d_forward(ops2d.image_to_act(x, dt, 8), w0, None, stem._packed, stem.stride, stem.pad, 0, dt, want_stats=False)[0]
-        h = ops2d.bn_relu_maxpool_forward(y, *stem._eval_coef.get(stem.bn_module), dt)      # relu(bn1(.)) inside the pool: not stored at full resolution
-        for layer in (enc.layer1, enc.layer2, enc.layer3, enc.layer4):
-            for blk in layer:
-                idn = h if blk._ud is None else ui(blk._ud, h, dt)
-                h = ui(blk._u2, ui(blk._u1, h, dt), dt, residual=idn, act=ACT_RELU)        # relu(bn2(conv2(.)) + identity) in conv2's epilogue
+        dt, ui = self.compute_dtype, _unit_infer
+        h = encoder_infer(self.model.encoder, x, dt)
         decoder_outputs, middle_masks = [], []
         for i, blk in enumerate(self.model.decoder.blocks):
             h = ui(blk._u2, ui(blk._u1, h, dt), dt)
@@ -447,3 +463,109 @@ class PCRLv2(nn.Module):
         features = [None] * 5 + [self.model.encoder.forward_last(x)]
         decoder_outputs, h, low = self.model.decoder(features, _mask_scales=() if mask_scale is None else (mask_scale,), _upsample=False)
         return decoder_outputs, h, (low[mask_scale] if mask_scale is not None else None)
+
+
+class ChestClassifier(nn.Module):
+    """The downstream model of the reference's README ("Load the Encoder Part of a 2D Model"):
+    `smp.Unet('resnet18', aux_params=dict(pooling='avg', dropout=0.2, activation='sigmoid', classes=n_class))` reduced to what a classifier runs --
+    `.encoder` (ResNetEncoder) and `.classification_head` = Sequential(AdaptiveAvgPool2d(1), Flatten, Dropout(p), Linear(512, n_class), Sigmoid), smp's
+    names (the linear layer is `classification_head.3`), initialised as smp's initialize_head does.  `encoder_weights`: a torchvision-named ResNet-18
+    state_dict or a 2D pre-training checkpoint ({'state_dict': encoder}); `fc.*` ignored.
+
+    loss(x, labels) is the training step's path (encoder.forward_last -> functions2d.ClsHeadFn), infer(x) the eval-mode one (the encoder on running
+    statistics through the inference kernels, the head without dropout); forward(x) returns probabilities in either mode."""
+
+    def __init__(self, n_class=14, dropout=0.2, encoder_weights=None):
+        super().__init__()
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError("dropout must be in [0, 1)")
+        self.encoder = ResNetEncoder(3)
+        self.classification_head = nn.Sequential(nn.AdaptiveAvgPool2d(1), nn.Flatten(), nn.Dropout(p=dropout, inplace=True),
+                                                 nn.Linear(self.encoder.out_channels[-1], n_class, bias=True), nn.Sigmoid())
+        initialize_head(self.classification_head)
+        self.n_class, self.dropout = n_class, float(dropout)
+        self.compute_dtype = config.default_compute_dtype()
+        self._pass_idx = 1
+        self.mask_generator = None        # a torch.Generator on the model's device: seeded dropout masks (None: torch's default generator)
+        if encoder_weights is not None:
+            sd = torch.load(encoder_weights, map_location="cpu", weights_only=False)
+            sd = sd.get("state_dict", sd)
+            self.encoder.load_state_dict({k: v for k, v in sd.items() if not k.startswith("fc.")})
+
+    # ---- engine controls, as on PCRLv2 ----
+    def set_compute_dtype(self, dt):
+        dt = {"fp32": torch.float32, "bf16": torch.bfloat16}.get(dt, dt) if isinstance(dt, str) else dt
+        if dt not in (torch.float32, torch.bfloat16):
+            raise ValueError("compute dtype must be float32 or bfloat16")
+        self.compute_dtype = dt
+        for u in self.encoder._units():
+            u.compute_dtype = dt
+        return self
+
+    def flush_counters(self):
+        for u in self.encoder._units():
+            u.flush_counters()
+
+    def state_dict(self, *args, **kwargs):
+        self.flush_counters()
+        return super().state_dict(*args, **kwargs)
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        for u in self.encoder._units():
+            u._pending = 0
+        out = super().load_state_dict(state_dict, *args, **kwargs)
+        ops.bump_weights_epoch()
+        return out
+
+    def _check(self, x):
+        if not x.is_cuda:
+            raise RuntimeError("ChestClassifier (pcrlv2_amd) runs on the GPU only: input is on %s and there is no CPU fallback" % x.device)
+
+    def draw_keep(self, n, device):
+        """The dropout keep mask of a training step: uint8 [n, 512], P(keep) = 1 - p, drawn on the device (`mask_generator` seeds it); None at p = 0."""
+        if self.dropout == 0.0:
+            return None
+        C = self.encoder.out_channels[-1]
+        return (torch.rand((n, C), device=device, generator=self.mask_generator) >= self.dropout).to(torch.uint8)
+
+    def loss(self, x, labels, keep=None):
+        """Training mode: -> (BCE loss 0-d, probabilities float32 [N, n_class] (no gradient)).  labels: uint8 [N, n_class] on the device.  `keep`: a
+        given dropout mask instead of a drawn one (tests)."""
+        self._check(x)
+        if not self.training:
+            raise RuntimeError("ChestClassifier.loss is the TRAINING step's path; in eval mode call infer")
+        ops2d.bump_stats_epoch()        # this forward moves running statistics: infer's cached eval-mode coefficients are stale
+        pass_idx = ops.next_pass()
+        self._pass_idx = pass_idx
+        for u in self.encoder._units():
+            u._pass_idx = pass_idx
+        h = self.encoder.forward_last(x)
+        if keep is None:
+            keep = self.draw_keep(x.shape[0], x.device)
+        lin = self.classification_head[3]
+        return Fn2.ClsHeadFn.apply(h, lin.weight, lin.bias, labels, keep, self.dropout if keep is not None else 0.0, self)
+
+    @torch.no_grad()
+    def infer(self, x, labels=None):
+        """Eval-mode probabilities float32 [N, n_class], whatever `self.training` says: nothing of the model is touched, no autograd graph.  With
+        labels (uint8 [N, n_class]) -> (probabilities, mean BCE loss 0-d) from the same launch."""
+        self._check(x)
+        dt = self.compute_dtype
+        h = encoder_infer(self.encoder, x, dt)
+        lin = self.classification_head[3]
+        probs, _, loss = ops2d.cls_head_forward(h, lin.weight, lin.bias, dt, labels=labels)
+        return probs if labels is None else (probs, loss)
+
+    @torch.no_grad()
+    def _forward_eval(self, x):
+        """model.eval()(x): the module chain pass by pass on the running statistics (encoder_eval), then the head without dropout."""
+        self._check(x)
+        dt = self.compute_dtype
+        lin = self.classification_head[3]
+        return ops2d.cls_head_forward(encoder_eval(self.encoder, x, dt), lin.weight, lin.bias, dt)[0]
+
+    def forward(self, x):
+        if not self.training:
+            return self._forward_eval(x)
+        labels = torch.zeros((x.shape[0], self.n_class), dtype=torch.uint8, device=x.device)
+        return self.loss(x, labels)[1]

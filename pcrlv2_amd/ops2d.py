@@ -496,3 +496,70 @@ def image_to_act(x, dtype, CP=8):
     out = new_act2(N, H, W, CP, dtype, x.device)
     lib().call("pcrl_nchw_to_nhwc_pad", x, out, N, C, H * W, CP, dtype_code(dtype), stream_handle())
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# supervised fine-tuning (csrc/cls_head.hip, csrc/auroc.hip)
+# ----------------------------------------------------------------------------------------------
+def _u8(t, shape, what):
+    if t.dtype != torch.uint8 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise PcrlError(f"{what} must be a contiguous uint8 tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def cls_head_forward(a, w, b, dtype, keep=None, p=0.0, labels=None):
+    """AdaptiveAvgPool2d(1) -> Flatten -> Dropout (keep: uint8 [N,C] mask, None = eval) -> Linear -> Sigmoid (-> BCELoss against labels uint8 [N,K])
+    on the NHWC activation a, one operator (pcrl_cls_head_fwd).  -> (probs float32 [N,K], pooled float32 [N,C], loss 0-d float32 | None)"""
+    L = lib()
+    N, H, W, C = dims2(a)
+    K = w.shape[0]
+    if a.dtype != dtype or tuple(w.shape) != (K, C) or w.dtype != torch.float32 or b.dtype != torch.float32:
+        raise PcrlError(f"cls_head_forward: activation {a.dtype} with {C} channels against a {tuple(w.shape)} {w.dtype} weight in {dtype}")
+    if keep is not None:
+        _u8(keep, (N, C), "cls_head_forward: keep")
+    probs, pooled = ops._f32(N * K, a.device).view(N, K), ops._f32(N * C, a.device).view(N, C)
+    loss, ws, nb = None, None, 0
+    if labels is not None:
+        _u8(labels, (N, K), "cls_head_forward: labels")
+        loss = ops._f32(1, a.device)
+        nb = L.call("pcrl_cls_head_ws_bytes", N)
+        ws = ops.workspace(nb, a.device)
+    L.call("pcrl_cls_head_fwd", a, keep, 1.0 / (1.0 - p) if keep is not None else 1.0, w.detach().contiguous(), b.detach(), labels, probs, pooled, loss, ws, nb,
+           N, H, W, C, K, dtype_code(dtype), stream_handle())
+    return probs, pooled, (loss.view(()) if loss is not None else None)
+
+
+def cls_head_backward(probs, labels, dloss, pooled, w, like, dtype, keep=None, p=0.0, need_da=True):
+    """Backward of cls_head_forward from d loss (pcrl_cls_head_bwd): `like` = the forward's activation (its shape only -- it is not read).
+    -> (da like `like` | None, dw float32 [K,C], db float32 [K])"""
+    N, H, W, C = dims2(like)
+    K = w.shape[0]
+    da = torch.empty_like(like) if need_da else None
+    dw, db = ops._f32(K * C, like.device).view(K, C), ops._f32(K, like.device)
+    lib().call("pcrl_cls_head_bwd", probs, _u8(labels, (N, K), "cls_head_backward: labels"), dloss.detach().reshape(1).float(), pooled, keep,
+               1.0 / (1.0 - p) if keep is not None else 1.0, w.detach().contiguous(), da, dw, db, N, H, W, C, K, dtype_code(dtype), stream_handle())
+    return da, dw, db
+
+
+def auroc_counts(probs, labels):
+    """int64 [K,3] on the device: per class (2 * #(positive > negative) + #(positive == negative), #positives, #negatives) -- pcrl_auroc_counts."""
+    M, K = probs.shape
+    if probs.dtype != torch.float32 or not probs.is_contiguous():
+        probs = probs.float().contiguous()
+    counts = torch.empty((K, 3), dtype=torch.int64, device=probs.device)
+    lib().call("pcrl_auroc_counts", probs, _u8(labels, (M, K), "auroc_counts: labels"), counts, M, K, stream_handle())
+    return counts
+
+
+def auroc_from_counts(counts):
+    """Host, float64: counts [K,3] (list or tensor) -> (per-class AUROC [K] float64 tensor, NaN where a class has no positive or no negative; their
+    mean over the classes that have one, NaN when none has)."""
+    rows = counts.tolist() if torch.is_tensor(counts) else counts
+    per = [float(c) / (2.0 * float(p) * float(q)) if p > 0 and q > 0 else float("nan") for c, p, q in rows]
+    valid = [v for v in per if v == v]
+    return torch.tensor(per, dtype=torch.float64), (sum(valid) / len(valid) if valid else float("nan"))
+
+
+def auroc(probs, labels):
+    """Per-class AUROC of probs float32 [M,K] against labels uint8 [M,K] (both on the device) by exact pair counting.  -> (per_class float64 [K], mean)"""
+    return auroc_from_counts(auroc_counts(probs, labels).cpu())
