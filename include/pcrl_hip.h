@@ -613,6 +613,18 @@ int pcrl_prep_resample(const int16_t* in, int16_t* out, int X, int Y, int Z, int
 int pcrl_prep_windows(const int16_t* vol, int X, int Y, int Z, const int64_t* rec, const double* prm, int W, int64_t max_src, int max_cols, double* out, int64_t out_len, int* stats, double* ws, int64_t ws_len, pcrl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * LUNA16 nodule candidates (csrc/luna_cubes.hip, host side pcrlv2_amd/luna_nodules.py): cubes around the points of candidates_V2.csv out of the
+ * 1 mm volume that pcrl_prep_resample leaves ([Z][Y][X] int16).
+ *   cubes      : out[m][i][j][k] = clip(vol[z0 + k][y0 + j][x0 + i], -1000, 1000) with (x0, y0, z0) = start[m][0..2] (int32 [M][3]; may be negative
+ *                or past the edge: a coordinate outside the volume gives -1000).  out_kind 0: int16 [M][CX][CY][CZ]; 1: float32 of the same shape
+ *                holding float32((double(v) + 1000.0) / 2000.0), the pre-task's normalisation.  CX, CY, CZ: positive multiples of 8, <= 64; anything
+ *                else is PCRL_EINVAL before any launch.  M = 0: nothing happens.  vol 2-byte, start 4-byte, out 16-byte aligned.  One launch, LDS
+ *                transpose, no atomics, no workspace: deterministic.
+ *   hu_to_unit : out[i] = float32((double(in[i]) + 1000.0) / 2000.0), no clip (for int16 cubes that come from disk); in and out 16-byte aligned. */
+int pcrl_prep_cubes(const int16_t* vol, int X, int Y, int Z, const int32_t* start, int M, void* out, int out_kind, int CX, int CY, int CZ, pcrl_stream_t stream);
+int pcrl_prep_hu_to_unit(const int16_t* in, float* out, int64_t n, pcrl_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Test hooks (NOT part of the drop-in surface; process-wide atomics, default 0 / tr 1 = the product path).  They select which
  * of the kernels behind one entry point runs, so that tests can check every kernel against the same reference and probes can
  * time them against each other inside one process (tools/conv_probe.py).  The state they set and the code tables live in csrc/core.hip.

@@ -557,3 +557,249 @@ def luna_pretask_loaders(args, device=None):
         return ev
 
     return _LazyLoaders(AugmentedLoader(x_train[rank::world], args.b, args.workers, device, True, seed + rank, drop_last=world > 1), make_eval)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# LUNA16 nodule candidates (the 3D downstream task: pcrlv2_amd/luna_nodules.py writes the cubes, models.NoduleClassifier reads them).
+# On disk: `<dir>/subset<f>/<series>_cand.npy` int16 [n, CX, CY, CZ] (HU clipped to [-1000, 1000]) + `<series>_cand_meta.npz` (world, label, index).
+# An ENTRY is (path of the _cand.npy, row, label).
+# ---------------------------------------------------------------------------------------------------------------
+NODULE_TRAIN_FOLDS = (0, 1, 2, 3, 4, 5, 6)
+CAND_SUFFIX, CAND_META_SUFFIX = "_cand.npy", "_cand_meta.npz"
+
+
+def luna_finetune_names(ratio: float, list_file: str = "train_val_txt/luna_train.txt"):
+    """The series kept for supervised training: the LAST 1 - ratio of `list_file`, `names[int(len * ratio):]` (utils.get_luna_finetune_list's rule; the
+    complement of luna_file_lists').  -> a set of names, or None (every series) when the list does not exist and ratio is 0.  A missing list with
+    ratio > 0 and an empty result end the run: --ratio is never silently ignored."""
+    if not os.path.exists(list_file):
+        if ratio > 0:
+            raise SystemExit(f"--ratio {ratio} needs the series list {list_file} (the last 1 - ratio of it is the supervised training set); it does not exist")
+        return None
+    with open(list_file) as f:
+        names = [line.strip("\n") for line in f]
+    names = names[int(len(names) * ratio):]
+    if not names:
+        raise SystemExit(f"--ratio {ratio} leaves no series of {list_file} for fine-tuning (the last 1 - ratio of the list is the supervised training set); "
+                         "lower --ratio")
+    return set(names)
+
+
+def candidate_entries(cubes_dir: str, folds, keep=None):
+    """-> [(path, row, label)] of every extracted candidate of the series (in `keep`, when given) of `folds`, in (fold, series, row) order."""
+    out = []
+    for fold in folds:
+        d = os.path.join(cubes_dir, "subset" + str(fold))
+        if not os.path.isdir(d):
+            continue
+        for f in sorted(os.listdir(d)):
+            if not f.endswith(CAND_SUFFIX) or (keep is not None and f[:-len(CAND_SUFFIX)] not in keep):
+                continue
+            path = os.path.join(d, f)
+            with np.load(path[:-len(CAND_SUFFIX)] + CAND_META_SUFFIX) as meta:
+                labels = meta["label"]
+            out += [(path, r, int(v)) for r, v in enumerate(labels)]
+    return out
+
+
+def balanced_epoch(labels, seed: int, epoch: int):
+    """One balanced epoch over entries with these labels: every positive once plus as many negatives (all of them when there are fewer), drawn
+    without replacement for THIS epoch, shuffled together.  A function of (seed, epoch) alone: the same on every rank.  -> int64 entry indices."""
+    labels = np.asarray(labels)
+    pos, neg = np.flatnonzero(labels != 0), np.flatnonzero(labels == 0)
+    rng = np.random.default_rng([int(seed), int(epoch)])
+    order = np.concatenate([pos, neg[rng.permutation(neg.size)[:pos.size]]])
+    return order[rng.permutation(order.size)].astype(np.int64)
+
+
+def rank_share(order, rank: int, world: int):
+    """The chest loader's sharding: the list cut to a multiple of `world`, every world-th element from `rank`."""
+    return order[:len(order) - len(order) % world][rank::world]
+
+
+class CandidateCubes(torch.utils.data.Dataset):
+    """(cube int16 [CX,CY,CZ], label int32 [1]) per item; rows are read with np.load(mmap_mode='r')[row].  `table` (a shared int64 tensor): item i is
+    entry table[i] -- BalancedCandidateLoader rewrites it before every epoch, the persistent workers see the new epoch through shared memory."""
+    _CACHE = 64
+
+    def __init__(self, entries, n=None, table=None):
+        self.entries, self.table = list(entries), table
+        self.n = len(self.entries) if n is None else n
+        self._maps = {}
+
+    def __len__(self):
+        return self.n
+
+    def _row(self, i):
+        path, row, label = self.entries[int(self.table[i]) if self.table is not None else i]
+        m = self._maps.get(path)
+        if m is None:
+            if len(self._maps) >= self._CACHE:
+                self._maps.pop(next(iter(self._maps)))
+            m = self._maps[path] = np.load(path, mmap_mode="r")
+        return np.array(m[row]), label        # a writable copy: torch.from_numpy refuses to share a read-only map quietly
+
+    def __getitem__(self, i):
+        cube, label = self._row(i)
+        return torch.from_numpy(cube), torch.tensor([label], dtype=torch.int32)
+
+
+class _SlotCandidates(CandidateCubes):
+    """CandidateCubes whose workers write straight into the shared batch slots (see _SlotCrops)."""
+
+    def __init__(self, entries, n, table, cube_buf, label_buf):
+        super().__init__(entries, n, table)
+        self.cube, self.label = cube_buf, label_buf
+
+    def __getitem__(self, key):
+        slot, row, i = key
+        cube, label = self._row(i)
+        self.cube[slot, row] = torch.from_numpy(cube)
+        self.label[slot, row, 0] = label
+        return slot, row
+
+
+class GpuCandidateAugment:
+    """__call__(cubes int16 [B,CX,CY,CZ], labels int32 [B,1], both on the host) -> (x [B,1,CX,CY,CZ] float32, y [B,1] uint8) on the device.
+    train: pcrl_prep_hu_to_unit -> the pre-task's spatial view (draw_spatial / apply_spatial: flip, +-10 degrees, 0.9-1.1) -> z-normalisation
+    (pcrl_aug_meanstd + pcrl_aug_znorm); no intensity transform.  eval: no spatial step."""
+
+    def __init__(self, device, seed, train):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("GpuCandidateAugment runs on the GPU (libpcrl_hip.so); there is no CPU fallback")
+        self.gen = torch.Generator(device=self.device).manual_seed(seed)
+        self.train = bool(train)
+
+    @torch.no_grad()
+    def __call__(self, cubes, labels):
+        c = cubes.to(self.device, non_blocking=True).contiguous()
+        y = labels.to(self.device, non_blocking=True).to(torch.uint8).view(-1, 1)
+        return normalise_cubes(c, self.gen if self.train else None), y
+
+
+def normalise_cubes(c, gen=None, unit=None):
+    """int16 cubes [B,CX,CY,CZ] on the device (or `unit`: float32 cubes already in [0, 1]) -> z-normalised float32 [B,1,CX,CY,CZ]; with a generator the
+    pre-task's spatial view is drawn and applied in between."""
+    if unit is None:
+        unit = torch.empty(c.shape, dtype=torch.float32, device=c.device)
+        _call("pcrl_prep_hu_to_unit", c, unit, c.numel())
+    B, S = unit.shape[0], unit[0].numel()
+    if gen is not None:
+        flip, inv = draw_spatial(gen, B, unit.device)
+        unit = apply_spatial(unit, flip, inv)
+    mean, rstd = torch.empty(B, dtype=torch.float32, device=unit.device), torch.empty(B, dtype=torch.float32, device=unit.device)
+    out = torch.empty_like(unit)
+    _call("pcrl_aug_meanstd", unit, mean, rstd, B, S)
+    _call("pcrl_aug_znorm", unit, out, mean, rstd, B, S)
+    return out.unsqueeze(1)
+
+
+class LunaCandidateKind:
+    """What AugmentedLoader needs to know about candidate cubes: a slot row is one int16 cube plus an int32 label.  The loader's `files` are entries
+    (path, row, label) -- or, with `table`, positions of a per-epoch table of entry indices (BalancedCandidateLoader)."""
+
+    def __init__(self, entries, train, shape=None, table=None):
+        self.entries, self.train, self.table = list(entries), bool(train), table
+        self.shape = tuple(shape) if shape is not None else tuple(np.load(self.entries[0][0], mmap_mode="r").shape[1:])
+
+    def slot_shapes(self):
+        return [(self.shape, torch.int16), ((1,), torch.int32)]
+
+    def slot_dataset(self, files, bufs):
+        return _SlotCandidates(self.entries, len(files), self.table, *bufs) if self.table is not None else _SlotCandidates(files, None, None, *bufs)
+
+    def dataset(self, files):
+        return CandidateCubes(self.entries, len(files), self.table) if self.table is not None else CandidateCubes(files)
+
+    def augment(self, device, seed):
+        return GpuCandidateAugment(device, seed, self.train)
+
+
+class BalancedCandidateLoader(AugmentedLoader):
+    """AugmentedLoader over balanced epochs (balanced_epoch) of candidate entries: the loader iterates the positions of a shared table that is
+    rewritten with this rank's share of the new epoch's draw before every pass.  The draw is seeded by (seed, epoch) and the same on every rank."""
+
+    def __init__(self, entries, batch_size, workers, device, seed=0, rank=0, world=1):
+        self.labels = np.array([e[2] for e in entries], dtype=np.int64)
+        self.sample_seed, self.rank, self.world, self.epoch = seed, rank, world, 0
+        n = len(rank_share(balanced_epoch(self.labels, seed, 0), rank, world))        # the same length every epoch
+        self.table = torch.zeros(max(n, 1), dtype=torch.int64).share_memory_()
+        super().__init__(list(range(n)), batch_size, workers, device, False, seed + rank, drop_last=world > 1,
+                         kind=LunaCandidateKind(entries, True, table=self.table))
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def __iter__(self):
+        share = rank_share(balanced_epoch(self.labels, self.sample_seed, self.epoch), self.rank, self.world)
+        self.table[:len(share)] = torch.from_numpy(np.ascontiguousarray(share))
+        self.epoch += 1
+        yield from super().__iter__()
+
+
+class SyntheticNoduleLoader:
+    """`--data synthetic` for the nodule classifier: (x [b,1,CX,CY,CZ] float32, y [b,1] uint8) on the device.  Unit noise; a "positive" carries a Gaussian
+    blob of fixed radius and amplitude at the centre, and the label is that fact: learning is observable."""
+    RADIUS, AMPLITUDE = 4.0, 3.0
+
+    def __init__(self, b, steps, shape=(64, 64, 32), seed=0, device=None):
+        self.device = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
+        self.b, self.steps, self.shape, self.seed = b, steps, tuple(shape), seed
+        self.g = torch.Generator(device=self.device).manual_seed(seed)
+        self.sharded = True                        # one stream per rank: nothing to cut
+        ax = [torch.arange(n, dtype=torch.float32, device=self.device) - (n - 1) / 2 for n in self.shape]
+        r2 = ax[0].view(-1, 1, 1) ** 2 + ax[1].view(1, -1, 1) ** 2 + ax[2].view(1, 1, -1) ** 2
+        self.blob = self.AMPLITUDE * torch.exp(-r2 / (2 * self.RADIUS ** 2))
+
+    def __len__(self):
+        return self.steps
+
+    def reset_rng(self):
+        self.g.manual_seed(self.seed)
+
+    def __iter__(self):
+        for _ in range(self.steps):
+            y = (torch.rand(self.b, 1, generator=self.g, device=self.device) < 0.5)
+            x = torch.randn((self.b, 1) + self.shape, generator=self.g, device=self.device)
+            yield x + y.view(-1, 1, 1, 1, 1).float() * self.blob, y.to(torch.uint8)
+
+
+def parse_folds(text):
+    """'7' or '8,9' -> (7,) or (8, 9)"""
+    return tuple(int(f) for f in str(text).split(",") if f.strip() != "")
+
+
+def nodule_loaders(args, device=None):
+    """{'train', 'eval', 'test'} over a directory of extracted candidate cubes: balanced epochs over folds 0-6 (without the validation and test folds;
+    only the series that --ratio keeps), --val_folds and --test_folds whole and unshuffled with the evaluation transform (this rank's contiguous
+    shard; built on first use).  Every loader yields (x [B,1,CX,CY,CZ] float32, y [B,1] uint8) on the device."""
+    from .data_chest import _LazyBuilt
+    device = device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu")
+    val_folds, test_folds = parse_folds(getattr(args, "val_folds", "7")), parse_folds(getattr(args, "test_folds", "8,9"))
+    keep = luna_finetune_names(args.ratio)
+    train = candidate_entries(args.data, [f for f in NODULE_TRAIN_FOLDS if f not in val_folds + test_folds], keep)
+    if not train:
+        raise SystemExit(f"no candidate cubes for training under {args.data} (folds 0-6 without --val_folds / --test_folds, --ratio {args.ratio}); "
+                         "write them with `python luna_nodules.py extract`")
+    n_pos = sum(1 for e in train if e[2])
+    if n_pos == 0:
+        raise SystemExit(f"the {len(train)} training candidates under {args.data} hold no positive: a balanced epoch would be empty")
+    print(f"total fine-tuning candidates {len(train)} ({n_pos} positive)")
+    rank = int(os.environ.get("RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    seed = getattr(args, "seed", 0)
+    shape = tuple(np.load(train[0][0], mmap_mode="r").shape[1:])
+
+    def held_out(folds, flag):
+        def make():
+            entries = candidate_entries(args.data, folds)
+            if not entries:
+                raise SystemExit(f"no candidate cubes in the folds {list(folds)} ({flag}) under {args.data}")
+            ev = AugmentedLoader(eval_shard(entries, rank, world), args.b, args.workers, device, False, seed, kind=LunaCandidateKind(entries, False, shape=shape))
+            ev.sharded = True
+            return ev
+        return make
+
+    return _LazyBuilt({"train": BalancedCandidateLoader(train, args.b, args.workers, device, seed, rank, world)},
+                      {"eval": held_out(val_folds, "--val_folds"), "test": held_out(test_folds, "--test_folds")})

@@ -197,6 +197,54 @@ _SKIPS = ("skip_out64", "skip_out128", "skip_out256", "out512")                 
 _UPSAMPLE = (4, 2, 1)                                                                                         # trilinear factors of the three masks (:125-127)
 
 
+# The encoder half of the two forwards, shared by PCRLv23d and NoduleClassifier (both hold the four `down_tr*` stages and `maxpool` under the
+# same names): one sequence of launches, whichever model asks.
+def _eval_luconv(m, h, dt, fused):
+    """One LUConv on its running statistics: the inference kernel (fused) or the module chain's two passes."""
+    c, n, gn = m.conv1, m.bn1, m._gn_groups
+    w = c.weight
+    if m._ci_pad:
+        h, w = ops.pad_first_layer(h, w, m._ci_pad, dt)
+    rm, rv = (None, None) if gn else (n.running_mean, n.running_var)
+    if fused:
+        return ops.luconv_infer(h, w, c.bias, n.weight, n.bias, rm, rv, m._packed, m._act, dt, gn_groups=gn, prelu=Fn._slope(m), inorm=m._inorm)
+    return ops.luconv_forward(h, w, c.bias, n.weight, n.bias, rm, rv,
+                              m._packed, m._act, dt, training=False, gn_groups=gn, prelu=Fn._slope(m), inorm=m._inorm)[0]
+
+
+def _eval_encoder(model, x, dt, fused, stash):
+    """-> `down_tr512`'s output on the running statistics.  stash: the stage outputs are kept as `skip_out64` ... `out512` (the reference's attributes)."""
+    h = x.float().contiguous()
+    for i, ((name, _, _), attr) in enumerate(zip(_ENCODER, _SKIPS)):
+        if i:
+            h = ops.maxpool_forward(ops.to_act(h, dt), dt)
+        st = getattr(model, name)
+        h = _eval_luconv(st.ops[1], _eval_luconv(st.ops[0], h, dt, fused), dt, fused)
+        if stash:
+            setattr(model, attr, h)
+    return h
+
+
+def _train_encoder(model, x, mine, lazy_skips, stash):
+    """-> `down_tr512`'s output in training mode.  `mine()` marks the stage modules with the pass number before every stage; lazy_skips: the
+    unpooled outputs of the first three stages are not stored (_LazySkip)."""
+    h, pooled = x, None
+    for i, ((name, _, _), attr) in enumerate(zip(_ENCODER, _SKIPS)):
+        stage = getattr(model, name)
+        mine()
+        h = h if i == 0 else (pooled if pooled is not None else model.maxpool(h))
+        last = stage.ops[1]
+        if config.FOLD_POOL_GRAD and i + 1 < len(_ENCODER) and not last._gn_groups:
+            # stage output and `self.maxpool` of it (:115-117) as one node: the pool's backward folds into the BatchNorm backward
+            a = stage.ops[0](h)
+            h, pooled = last.forward_pooled(a, pool_only=lazy_skips)     # lazy_skips: h is a _LazySkip (the stage output is not stored)
+        else:
+            h, pooled = stage(h), None
+        if stash:
+            setattr(model, attr, h)          # the reference keeps these alive as attributes; the skips are never consumed (D6)
+    return h
+
+
 class PCRLv23d(nn.Module):
     """reference: models/pcrlv2_model_3d.py:95-133"""
 
@@ -267,26 +315,8 @@ class PCRLv23d(nn.Module):
 
     def _eval_stages(self, x, local, fused, features_only=False):
         dt = self.compute_dtype
-
-        def lu(m, h):
-            c, n, gn = m.conv1, m.bn1, m._gn_groups
-            w = c.weight
-            if m._ci_pad:
-                h, w = ops.pad_first_layer(h, w, m._ci_pad, dt)
-            rm, rv = (None, None) if gn else (n.running_mean, n.running_var)
-            if fused:
-                return ops.luconv_infer(h, w, c.bias, n.weight, n.bias, rm, rv, m._packed, m._act, dt, gn_groups=gn, prelu=Fn._slope(m), inorm=m._inorm)
-            return ops.luconv_forward(h, w, c.bias, n.weight, n.bias, rm, rv,
-                                      m._packed, m._act, dt, training=False, gn_groups=gn, prelu=Fn._slope(m), inorm=m._inorm)[0]
-
-        h = x.float().contiguous()
-        for i, ((name, _, _), attr) in enumerate(zip(_ENCODER, _SKIPS)):
-            if i:
-                h = ops.maxpool_forward(ops.to_act(h, dt), dt)
-            st = getattr(self, name)
-            h = lu(st.ops[1], lu(st.ops[0], h))
-            if not fused:
-                setattr(self, attr, h)
+        lu = lambda m, h: _eval_luconv(m, h, dt, fused)     # noqa: E731
+        h = _eval_encoder(self, x, dt, fused, stash=not fused)
         feats, masks = [], []
         for (name, _, _), factor in zip(_DECODER, _UPSAMPLE):
             up = getattr(self, name)
@@ -314,19 +344,7 @@ class PCRLv23d(nn.Module):
             for m in mods:
                 m._pass_idx = pass_idx
 
-        h, pooled = x, None
-        for i, ((name, _, _), attr) in enumerate(zip(_ENCODER, _SKIPS)):
-            stage = getattr(self, name)
-            mine()
-            h = h if i == 0 else (pooled if pooled is not None else self.maxpool(h))
-            last = stage.ops[1]
-            if config.FOLD_POOL_GRAD and i + 1 < len(_ENCODER) and not last._gn_groups:
-                # stage output and `self.maxpool` of it (:115-117) as one node: the pool's backward folds into the BatchNorm backward
-                a = stage.ops[0](h)
-                h, pooled = last.forward_pooled(a, pool_only=lazy_skips)     # lazy_skips: h is a _LazySkip (the stage output is not stored)
-            else:
-                h, pooled = stage(h), None
-            setattr(self, attr, h)          # the reference keeps these alive as attributes; the skips are never consumed (D6)
+        h = _train_encoder(self, x, mine, lazy_skips, stash=True)
         middle_features, middle_masks = [], []
         for (name, _, _), factor in zip(_DECODER, _UPSAMPLE):
             mine()
@@ -374,3 +392,128 @@ def _skip_attribute(name):
 for _n in _SKIPS[:3]:
     setattr(PCRLv23d, _n, _skip_attribute(_n))
 
+
+
+class NoduleClassifier(nn.Module):
+    """The downstream model of the 3D encoder: LUNA16 nodule false-positive reduction, the paper's 3D classification task (the reference's fine-tune
+    branch is not public).  `down_tr64 / 128 / 256 / 512` and `maxpool` are PCRLv23d's, under PCRLv23d's names -- the encoder keys of a 3D pre-training
+    checkpoint are this model's -- and `classification_head` = Sequential(AdaptiveAvgPool3d(1), Flatten, Dropout(p), Linear(512, n_class), Sigmoid), a
+    parameter container laid out as ChestClassifier's (the linear layer is `classification_head.3`).  `encoder_weights`: a 3D pre-training checkpoint
+    ({'state_dict': PCRLv23d's}); its `down_tr*` entries must be exactly the encoder's, everything else in it is ignored.
+
+    loss(x, labels) is the training step's path (the encoder half of PCRLv23d's training forward -> functions2d.ClsHeadFn on `down_tr512`'s NDHWC output
+    viewed as NHWC [N, D/8 * H/8, W/8, 512]), infer(x) the eval-mode one (the encoder on running statistics through the inference kernels, the head
+    without dropout); forward(x) returns probabilities in either mode.  The interface is ChestClassifier's."""
+
+    def __init__(self, n_class=1, dropout=0.2, encoder_weights=None, act='relu', norm='bn', in_channels=1):
+        super().__init__()
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError("dropout must be in [0, 1)")
+        self.compute_dtype = config.default_compute_dtype()
+        self.maxpool = _MaxPool3d2()
+        for name, cin, depth in _ENCODER:
+            setattr(self, name, DownTransition(in_channels if cin is None else cin, depth, act, norm))
+        self.classification_head = nn.Sequential(nn.AdaptiveAvgPool3d(1), nn.Flatten(), nn.Dropout(p=dropout, inplace=True),
+                                                 nn.Linear(512, n_class, bias=True), nn.Sigmoid())
+        nn.init.xavier_uniform_(self.classification_head[3].weight)        # as ChestClassifier's head (smp's initialize_head)
+        nn.init.constant_(self.classification_head[3].bias, 0)
+        self.n_class, self.dropout = n_class, float(dropout)
+        self._pass_idx = 1
+        self.mask_generator = None        # a torch.Generator on the model's device: seeded dropout masks (None: torch's default generator)
+        if encoder_weights is not None:
+            self.load_encoder(encoder_weights)
+
+    def load_encoder(self, path):
+        """The `down_tr*` entries of a 3D pre-training checkpoint's 'state_dict' -> the encoder, strictly: a missing or an unknown encoder key raises."""
+        ckpt = torch.load(path, map_location="cpu", weights_only=False)
+        if not isinstance(ckpt, dict) or "state_dict" not in ckpt:
+            raise KeyError(f"{path}: no 'state_dict' entry (a 3D pre-training checkpoint is expected)")
+        strip = lambda k: k[len("module."):] if k.startswith("module.") else k      # noqa: E731  (a checkpoint saved from under nn.DataParallel)
+        enc = {strip(k): v for k, v in ckpt["state_dict"].items() if strip(k).startswith("down_tr")}
+        own = {k for k in self.state_dict() if k.startswith("down_tr")}
+        if set(enc) != own:
+            raise KeyError(f"{path}: encoder keys differ from the model's: missing {sorted(own - set(enc))[:4]}, unexpected {sorted(set(enc) - own)[:4]}")
+        self.load_state_dict(enc, strict=False)
+
+    # ---- engine controls: PCRLv23d's (they walk self.modules()) ----
+    set_compute_dtype = PCRLv23d.set_compute_dtype
+    flush_counters = PCRLv23d.flush_counters
+    _stage_modules = PCRLv23d._stage_modules
+
+    def state_dict(self, *args, **kwargs):
+        self.flush_counters()
+        return super().state_dict(*args, **kwargs)
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        for m in self.modules():
+            if isinstance(m, _Counted):
+                m._pending = 0
+        out = super().load_state_dict(state_dict, *args, **kwargs)
+        ops.bump_weights_epoch()
+        return out
+
+    def _check(self, x):
+        if not x.is_cuda:
+            raise RuntimeError("NoduleClassifier (pcrlv2_amd) runs on the GPU only: input is on %s and there is no CPU fallback" % x.device)
+
+    def draw_keep(self, n, device):
+        """The dropout keep mask of a training step: uint8 [n, 512], P(keep) = 1 - p, drawn on the device (`mask_generator` seeds it); None at p = 0."""
+        if self.dropout == 0.0:
+            return None
+        return (torch.rand((n, 512), device=device, generator=self.mask_generator) >= self.dropout).to(torch.uint8)
+
+    def _head_input(self, h):
+        """`down_tr512`'s output [N,512,D,H,W] (NDHWC memory) as the NHWC activation [N, D * H, W, 512] the head kernels take: a view."""
+        h = ops.to_act(h, self.compute_dtype)
+        N, D, H, W, C = ops.dims(h)
+        return h.permute(0, 2, 3, 4, 1).reshape(N, D * H, W, C).permute(0, 3, 1, 2)
+
+    def loss(self, x, labels, keep=None):
+        """Training mode: -> (BCE loss 0-d, probabilities float32 [N, n_class] (no gradient)).  labels: uint8 [N, n_class] on the device.  `keep`: a
+        given dropout mask instead of a drawn one (tests)."""
+        self._check(x)
+        if not self.training:
+            raise RuntimeError("NoduleClassifier.loss is the TRAINING step's path; in eval mode call infer")
+        from .. import functions2d as Fn2
+        pass_idx = ops.next_pass()
+        self._pass_idx = pass_idx
+        mods = self._stage_modules()
+
+        def mine():
+            for m in mods:
+                m._pass_idx = pass_idx
+
+        h = _train_encoder(self, x, mine, lazy_skips=True, stash=False)
+        if keep is None:
+            keep = self.draw_keep(x.shape[0], x.device)
+        lin = self.classification_head[3]
+        out = Fn2.ClsHeadFn.apply(self._head_input(h), lin.weight, lin.bias, labels, keep, self.dropout if keep is not None else 0.0, self)
+        ops.end_of_forward_join()
+        return out
+
+    def _eval_probs(self, x, fused, labels=None):
+        from .. import ops2d
+        dt = self.compute_dtype
+        h = _eval_encoder(self, x, dt, fused, stash=False)
+        lin = self.classification_head[3]
+        probs, _, loss = ops2d.cls_head_forward(self._head_input(h), lin.weight, lin.bias, dt, labels=labels)
+        return probs if labels is None else (probs, loss)
+
+    @torch.no_grad()
+    def infer(self, x, labels=None):
+        """Eval-mode probabilities float32 [N, n_class], whatever `self.training` says: nothing of the model is touched, no autograd graph.  With
+        labels (uint8 [N, n_class]) -> (probabilities, mean BCE loss 0-d) from the same launch."""
+        self._check(x)
+        return self._eval_probs(x, True, labels)
+
+    @torch.no_grad()
+    def _forward_eval(self, x):
+        """model.eval()(x): the module chain pass by pass on the running statistics, then the head without dropout."""
+        self._check(x)
+        return self._eval_probs(x, False)
+
+    def forward(self, x):
+        if not self.training:
+            return self._forward_eval(x)
+        labels = torch.zeros((x.shape[0], self.n_class), dtype=torch.uint8, device=x.device)
+        return self.loss(x, labels)[1]

@@ -31,7 +31,8 @@ from .utils import AverageMeter, adjust_learning_rate
 
 
 def train_step(model, optimizer, batch):
-    """One optimisation step on (x [B,3,H,W] float32, y [B,K] uint8).  -> (loss, probabilities), detached."""
+    """One optimisation step on (x [B,3,H,W] float32, y [B,K] uint8) -- or the 3D classifier's [B,1,X,Y,Z] cubes.  -> (loss, probabilities), detached.
+    `model.provision_key` (train_classifier sets it) names the workload in the allocator's provisioning table."""
     _ops.begin_step()
     _fn.reset_parked()
     dev = next(model.parameters()).device
@@ -42,7 +43,7 @@ def train_step(model, optimizer, batch):
     loss.backward(gradient=_fn.root_gradient(loss))
     optimizer.step()
     _ops.throttle_host(dev, step_done=True)
-    _ops.provision_allocator(dev, key=("2d-finetune", tuple(x.shape)))
+    _ops.provision_allocator(dev, key=(getattr(model, "provision_key", "2d-finetune"), tuple(x.shape)))
     return loss.detach(), probs.detach()
 
 
@@ -120,11 +121,26 @@ def _fmt(val):
 
 
 def train_chest_classifier(args, loaders):
+    def make_model():
+        enc_w = getattr(args, "encoder_weights", None) or None
+        if args.phase == "finetune" and enc_w is None:
+            raise SystemExit("--phase finetune needs --encoder_weights (a 2D pre-training checkpoint or a ResNet-18 state_dict); to train the classifier from "
+                             "random weights use --phase scratch")
+        return ChestClassifier(n_class=int(getattr(args, "n_class", 14)), dropout=float(getattr(args, "dropout", 0.2)),
+                               encoder_weights=enc_w if args.phase == "finetune" else None)
+
+    return train_classifier(args, loaders, make_model, "2d-finetune")
+
+
+def train_classifier(args, loaders, make_model, key):
+    """The supervised loop for any model with ChestClassifier's interface (.loss(x, y), .infer(x, labels=), .n_class, .set_compute_dtype,
+    .mask_generator): `make_model()` builds it on the host once the process group stands and the seeds are set; `key` names the workload for the
+    allocator's provisioning.  -> the trained model (`.test_metrics`: the final test's)."""
     distributed = int(os.environ.get("WORLD_SIZE", "1")) > 1
     owns_group = distributed and not (dist.is_available() and dist.is_initialized())
     ok = False
     try:
-        model = _train_chest_classifier(args, loaders, distributed)
+        model = _train_classifier(args, loaders, make_model, key, distributed)
         ok = True
         return model
     finally:
@@ -132,19 +148,15 @@ def train_chest_classifier(args, loaders):
             _ddp.shutdown(ok)
 
 
-def _train_chest_classifier(args, loaders, distributed):
+def _train_classifier(args, loaders, make_model, key, distributed):
     rank = 0
     if distributed:
         rank, _, local_rank = _ddp.init_process_group_from_env()
         torch.cuda.set_device(local_rank)
     seed_everything(getattr(args, "seed", 42))
     chatty = rank == 0
-    enc_w = getattr(args, "encoder_weights", None) or None
-    if args.phase == "finetune" and enc_w is None:
-        raise SystemExit("--phase finetune needs --encoder_weights (a 2D pre-training checkpoint or a ResNet-18 state_dict); to train the classifier from "
-                         "random weights use --phase scratch")
-    model = ChestClassifier(n_class=int(getattr(args, "n_class", 14)), dropout=float(getattr(args, "dropout", 0.2)),
-                            encoder_weights=enc_w if args.phase == "finetune" else None).cuda()
+    model = make_model().cuda()
+    model.provision_key = key
     dev = next(model.parameters()).device
     model.mask_generator = torch.Generator(device=dev).manual_seed(int(getattr(args, "seed", 42)) + 104729 * (rank + 1))
     if getattr(args, "amp", False):
@@ -166,6 +178,8 @@ def _train_chest_classifier(args, loaders, distributed):
     best, last_epoch = None, None
     for epoch in range(first_epoch, args.epochs + 1):
         adjust_learning_rate(epoch, args, optimizer)
+        if hasattr(loaders['train'], 'set_epoch'):
+            loaders['train'].set_epoch(epoch)       # a resumed run continues the sequence of per-epoch draws
         if chatty:
             print("==> training...")
         t_start = time.time()
