@@ -426,6 +426,9 @@ int pcrl_conv2d_pack_s2(const float* w_ref, void* out, int Co, int Ci, int KH, i
 int pcrl_conv2d_dgrad_s2(const void* dy, const void* wp_class, void* dx, int N, int Hi, int Wi, int Ci, int Ho, int Wo, int CoP, int KH, int KW,
                          int a, int b, int dtype, pcrl_stream_t stream);
 size_t pcrl_conv2d_wgrad_ws_bytes(int N, int Ho, int Wo, int CiP, int CoP, int KH, int KW);
+/* which kernel pcrl_conv2d_wgrad runs for a geometry (no launch; follows the wgrad test hooks): 0 gather, 1 right-sized narrow kernel (16/32-channel
+ * layers), 2 LDS-halo brick kernel, 3 one kernel row per block */
+int64_t pcrl_conv2d_wgrad_kind(int N, int Hi, int Wi, int CiP, int Ho, int Wo, int CoP, int KH, int KW, int stride, int pad, int up, int dtype);
 int pcrl_conv2d_wgrad(const void* x, const void* dy, float* dw_ref, void* ws, size_t ws_bytes, int N, int Hi, int Wi, int CiP, int Ci_out,
                       int Ho, int Wo, int CoP, int KH, int KW, int stride, int pad, int up, int dtype, pcrl_stream_t stream);
 

@@ -1505,6 +1505,10 @@ static Conv2dWgradRoute conv2d_wgrad_route(int N, int Hi, int Wi, int CiP, int H
   if (same3 && pcrl_wgrad_brick2d_eligible(N, Ho, Wo, CiP, CoP, dtype)) return CONV2D_WG_BRICK;
   return wgrad2d_row3_ok(CiP, CoP, KH, KW, dtype) ? CONV2D_WG_ROW3 : CONV2D_WG_GATHER;
 }
+// which kernel pcrl_conv2d_wgrad runs for a geometry (no launch): 0 gather, 1 right-sized narrow kernel, 2 LDS-halo brick kernel, 3 one kernel row per block
+extern "C" int64_t pcrl_conv2d_wgrad_kind(int N, int Hi, int Wi, int CiP, int Ho, int Wo, int CoP, int KH, int KW, int stride, int pad, int up, int dtype) {
+  return conv2d_wgrad_route(N, Hi, Wi, CiP, Ho, Wo, CoP, KH, KW, stride, pad, up, dtype);
+}
 
 extern "C" size_t pcrl_conv2d_wgrad_ws_bytes(int N, int Ho, int Wo, int CiP, int CoP, int KH, int KW) {
   // the largest of the variants (the dtype is not known here)
