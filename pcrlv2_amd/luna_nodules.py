@@ -22,7 +22,6 @@ from __future__ import annotations
 import argparse
 import concurrent.futures as cf
 import os
-import subprocess
 import sys
 from typing import NamedTuple
 
@@ -184,17 +183,8 @@ def extract(args, log=print):
 def train(args):
     if args.phase == "finetune" and not args.encoder_weights:
         raise SystemExit("--phase finetune needs --encoder_weights (a 3D pre-training checkpoint); to train the classifier from random weights use --phase scratch")
-    os.makedirs(args.output, exist_ok=True)
-    ids = [g for g in args.gpus.split(',') if g != '']
-    if len(ids) > 1 and "WORLD_SIZE" not in os.environ:
-        env = dict(os.environ, HIP_VISIBLE_DEVICES=args.gpus, HSA_ENABLE_IPC_MODE_LEGACY="0")
-        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={len(ids)}", "--master-addr", "127.0.0.1",
-               "--master-port", os.environ.get("MASTER_PORT", "29511"), os.path.abspath(sys.argv[0])] + sys.argv[1:]
-        raise SystemExit(subprocess.call(cmd, env=env))
-    if "WORLD_SIZE" not in os.environ:
-        os.environ["HIP_VISIBLE_DEVICES"] = args.gpus
-    os.environ.setdefault("PCRL_LOADER_WORKERS", str(args.workers))
-    print(args)
+    from .main import launch
+    launch(args)
     from .data import SyntheticNoduleLoader, nodule_loaders
     from .models import NoduleClassifier
     from .train_finetune import train_classifier

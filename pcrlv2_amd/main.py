@@ -20,9 +20,6 @@ import subprocess
 import sys
 import warnings
 
-warnings.filterwarnings('ignore')
-
-
 # flag, default, type (None = store_true), help -- the reference's flags (main.py:22-39) with their defaults
 _FLAGS = (
     ("data", "/data1/luchixiang/LUNA16/processed", str, "dataset directory, or 'synthetic'"),
@@ -211,9 +208,10 @@ def check_route(args):
         raise SystemExit("--n_class {}: 1..31".format(args.n_class))
 
 
-def main(argv=None):
-    args = build_parser().parse_args(argv)
-    check_route(args)
+def launch(args):
+    """In front of every training run: the output directory; with several ids in --gpus and no launcher above, this script again under
+    torch.distributed.run, one process per GPU (this process then ends with the launcher's exit code); the visible devices; the loader workers'
+    share of the CPUs; the parsed flags on the first line of the log."""
     os.makedirs(args.output, exist_ok=True)
     ids = [g for g in args.gpus.split(',') if g != '']
     if len(ids) > 1 and "WORLD_SIZE" not in os.environ:
@@ -225,6 +223,13 @@ def main(argv=None):
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpus
     os.environ.setdefault("PCRL_LOADER_WORKERS", str(args.workers))     # ddp.bind_rank_to_numa keeps this many CPUs of the rank's share for the loader workers
     print(args)
+
+
+def main(argv=None):
+    warnings.filterwarnings('ignore')       # the command line's choice (the reference's main.py:10), not an importer's
+    args = build_parser().parse_args(argv)
+    check_route(args)
+    launch(args)
     data_loader = get_dataloader(args)
     if args.model == 'pcrlv2' and args.phase == 'pretask' and args.d == 3:
         from .train_3d import train_pcrlv2_3d

@@ -1,9 +1,8 @@
 """2D pre-training loop on the MI355X engine -- drop-in for the reference's train_2d.py  (SURVEY 8f N1).
 
 Same entry point `train_pcrlv2(args, data_loader, out_channel=3)`, `cos_loss`, loss assembly (five scales, no divergence guard,
-train_2d.py:139-171), LR schedule, log line and checkpoint (the ENCODER's state_dict only, train_2d.py:99).  The deliberate
-differences are those listed in pcrlv2_amd/train_3d.py (bf16 for --amp, one process per GPU instead of nn.DataParallel, lazy
-meters, --seed honoured).  `--encoder_weights FILE` initialises the encoder from a local torchvision-named ResNet-18 state_dict (the
+train_2d.py:139-171), LR schedule, log line and checkpoint (the ENCODER's state_dict only, train_2d.py:99).  The run, the epoch and the
+bracket around a step are pcrlv2_amd.loop's, which also lists the deliberate differences.  `--encoder_weights FILE` initialises the encoder from a local torchvision-named ResNet-18 state_dict (the
 reference downloads ImageNet weights at construction, pcrlv2_model.py:200; offline the default is random init, with a warning).
 `--resume CKPT` continues from a checkpoint of the reference's 2D layout: that layout holds the ENCODER only (train_2d.py:99), so
 the encoder, the epoch counter and -- when the shapes match -- the momentum buffers are restored, the decoder and heads restart.
@@ -13,23 +12,19 @@ from __future__ import print_function
 import math
 import os
 import random
-import sys
-import time
 
 import torch
-import torch.distributed as dist
 
-from . import config as _cfg
-from . import ddp as _ddp
 from . import functions as _fn
+from . import loop as _loop
 from . import ops as _ops
 from . import ops2d as _ops2d
 from .functions2d import MaskMSEFn, SegMSEFn, mse_loss2d
+from .loop import to_gpu
 from .models.pcrlv2_model import PCRLv2
 from .optim import FusedSGD
-from .train_3d import BETA_PERIOD, COS_MAX_TERMS, CosineSimilarityMean, _fused_cos_losses, _to_gpu, cos_loss, seed_everything  # noqa: F401  (cos_loss: train_2d.py:111-117)
-from .train_3d import _val_shard, val_beta
-from .utils import AverageMeter, adjust_learning_rate
+from .train_3d import BETA_PERIOD, COS_MAX_TERMS, LOGGED, CosineSimilarityMean, cos_loss, fused_cos_losses  # noqa: F401  (cos_loss: train_2d.py:111-117)
+from .train_3d import lower_total, mean_scales, val_beta, val_text
 
 
 class MSELoss2d:
@@ -55,8 +50,8 @@ def step_losses(model, batch, epoch, criterion, cosine):
     the local views concatenated in one launch, both restoration terms against the NCHW image without a layout copy, the total in one."""
     view1, view2, target, _unused_gt2, local_views = batch
     n = view1.size(0)
-    target = _to_gpu(target)
-    view1, view2 = _to_gpu(view1), _to_gpu(view2)
+    target = to_gpu(target)
+    view1, view2 = to_gpu(view1), to_gpu(view2)
     nl = len(local_views)
     fused = (FUSED_STEP_2D and isinstance(model, PCRLv2) and isinstance(criterion, MSELoss2d) and getattr(cosine, "fusable", False)
              and 2 + 4 * nl <= COS_MAX_TERMS)
@@ -68,10 +63,10 @@ def step_losses(model, batch, epoch, criterion, cosine):
         feats1, h1, low1 = model.forward_engine(view1, mask_scale=scale)
         with _ops.view_pass(view2.device, view2, path2d=True):
             feats2, _, _ = model.forward_engine(view2)
-        loc = _ops.concat_batch([_to_gpu(v) for v in local_views])
+        loc = _ops.concat_batch([to_gpu(v) for v in local_views])
         feats_loc, _, _ = model.forward_engine(loc)
         _ops.join_side_stream()                    # the cosine terms read both views' features on the main stream
-        cos2, _ = _fused_cos_losses(feats1, feats2, feats_loc, n, nl, draws=draws)
+        cos2, _ = fused_cos_losses(feats1, feats2, feats_loc, n, nl, draws=draws)
         seg = model.model.segmentation_head[0]
         l_restore = SegMSEFn.apply(h1, seg.weight, seg.bias, target, model._seg)
         l_deep_raw = MaskMSEFn.apply(low1, target, 2 ** (ns - 1 - scale))
@@ -83,7 +78,7 @@ def step_losses(model, batch, epoch, criterion, cosine):
         feats2, _mask2, _ = model(view2)
     _ops.join_side_stream()                        # the cosine term below reads both views' features on the main stream
     l_global, scale = cos_loss(cosine, feats1, feats2)
-    feats_loc, _, _ = model(torch.cat([_to_gpu(v) for v in local_views], dim=0), local=True)
+    feats_loc, _, _ = model(torch.cat([to_gpu(v) for v in local_views], dim=0), local=True)
     return assemble_losses(feats1, feats2, feats_loc, mask1, masks1, target, n, len(local_views), epoch, criterion, cosine, first=(l_global, scale))
 
 
@@ -109,17 +104,7 @@ def assemble_losses(feats1, feats2, feats_loc, mask1, masks1, target, n, nlocal,
 
 
 def train_step(model, optimizer, batch, epoch, criterion, cosine):
-    _ops.begin_step()
-    _fn.reset_parked()
-    dev = next(model.parameters()).device
-    _ops.throttle_host(dev)      # at most config.MAX_STEPS_AHEAD steps of host run-ahead (allocator footprint, see config.py)
-    losses = step_losses(model, batch, epoch, criterion, cosine)
-    optimizer.zero_grad()
-    losses[0].backward(gradient=_fn.root_gradient(losses[0]))
-    optimizer.step()
-    _ops.throttle_host(dev, step_done=True)
-    # first complete step of this batch shape: size the allocator's per-stream pools for the steady state, once (ops.provision_allocator)
-    _ops.provision_allocator(dev, key=("2d", tuple(batch[0].shape), len(batch[4])))
+    losses = _loop.run_step(model, optimizer, lambda: step_losses(model, batch, epoch, criterion, cosine), ("2d", tuple(batch[0].shape), len(batch[4])))
     return tuple(l.detach() for l in losses)
 
 
@@ -128,13 +113,10 @@ VAL_KEYS = (("mse_out",) + tuple("mse_mid%d" % k for k in range(NUM_SCALES)) + t
             + tuple("cos_local%d" % k for k in range(NUM_SCALES)))
 
 
-def _mean_scales(m, name):
-    return sum(m[name + str(k)] for k in range(NUM_SCALES)) / NUM_SCALES
-
-
 def val_total(m, epoch):
     """The expectation of the training loss (train_2d.py:139-168) over its uniform scale draws, from the sixteen per-scale means."""
-    return m["mse_out"] + _mean_scales(m, "cos_global") + _mean_scales(m, "cos_local") + val_beta(epoch) * _mean_scales(m, "mse_mid")
+    mean = lambda name: mean_scales(m, name, NUM_SCALES)        # noqa: E731
+    return m["mse_out"] + mean("cos_global") + mean("cos_local") + val_beta(epoch) * mean("mse_mid")
 
 
 def validate(model, loader, epoch, group=None):
@@ -146,23 +128,18 @@ def validate(model, loader, epoch, group=None):
     loader's augmentation draws are reset to its seed first (`reset_rng()`): every pass sees the same data, two passes on the same weights give
     bit-identical numbers.  `model.training` is not changed.
     -> {'mse_out', 'mse_mid0..4', 'cos_global0..4', 'cos_local0..4', 'total', 'n'}; sample-weighted means (a ragged last batch counts by its size)."""
-    dev = next(model.parameters()).device
-    if hasattr(loader, "reset_rng"):
-        loader.reset_rng()
-    distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
-    acc = torch.zeros(len(VAL_KEYS) + 1, dtype=torch.float64, device=dev)
-    with torch.no_grad():
-        for batch in (_val_shard(loader, group) if distributed else loader):
-            view1, view2, target, _gt2, local_views = batch
-            view1, view2, target = _to_gpu(view1), _to_gpu(view2), _to_gpu(target)
-            feats1, out1, masks1 = model.infer(view1, upsample=False)
-            feats2, _, _ = model.infer(view2, features_only=True)
-            loc = _ops.concat_batch([_to_gpu(v) for v in local_views])
-            feats_loc, _, _ = model.infer(loc, local=True, features_only=True)
-            _ops2d.val2d_metrics(out1, masks1, target, feats1, feats2, feats_loc, acc)
-    if distributed:
-        dist.all_reduce(acc, group=group)
-    host = acc.cpu().tolist()          # the pass's one synchronisation
+    acc = torch.zeros(len(VAL_KEYS) + 1, dtype=torch.float64, device=next(model.parameters()).device)
+
+    def per_batch(batch):
+        view1, view2, target, _gt2, local_views = batch
+        view1, view2, target = to_gpu(view1), to_gpu(view2), to_gpu(target)
+        feats1, out1, masks1 = model.infer(view1, upsample=False)
+        feats2, _, _ = model.infer(view2, features_only=True)
+        loc = _ops.concat_batch([to_gpu(v) for v in local_views])
+        feats_loc, _, _ = model.infer(loc, local=True, features_only=True)
+        _ops2d.val2d_metrics(out1, masks1, target, feats1, feats2, feats_loc, acc)
+
+    host = _loop.held_out_pass(loader, group, acc, per_batch)
     n = host[-1]
     out = {k: (v / n if n else float("nan")) for k, v in zip(VAL_KEYS, host)}
     out["total"] = val_total(out, epoch)
@@ -170,120 +147,49 @@ def validate(model, loader, epoch, group=None):
     return out
 
 
-def _best_checkpoint_name(args):
-    return os.path.join(args.output, "{}_{}_{}_{}_best.pt".format(args.model, args.n, args.phase, args.ratio))
+def resume_encoder(path, model, optimizer, rank):
+    """`--resume`: the 2D checkpoint layout holds the ENCODER only (train_2d.py:99).  -> the stored epoch"""
+    ckpt = torch.load(path, map_location="cpu", weights_only=False)
+    model.model.encoder.load_state_dict(ckpt["state_dict"])
+    try:
+        optimizer.load_state_dict(ckpt["optimizer"])
+    except (ValueError, KeyError) as e:       # a checkpoint of another parameter list (group / size mismatch): keep fresh momentum, say so on EVERY rank
+        print("==> [rank {}] optimizer state not restored: {}".format(rank, e))
+    return int(ckpt.get("epoch", -1))
 
 
-def save_if_best(args, model, optimizer, epoch, val, best):
-    """--save_best: the 2D checkpoint layout (train_2d.py:96-107: the ENCODER's state_dict) plus 'val' (validate's dict), written whenever `total`
-    improves strictly.  -> the best total so far."""
-    if best is not None and not val["total"] < best:
-        return best
-    if hasattr(model, "flush_counters"):
-        model.flush_counters()
-    torch.save({'opt': args, 'state_dict': model.model.encoder.state_dict(), 'optimizer': optimizer.state_dict(), 'epoch': epoch, 'val': dict(val)},
-               _best_checkpoint_name(args))
-    return val["total"]
+def encoder_state(model):
+    """What a 2D checkpoint holds under 'state_dict' (train_2d.py:96-107: the ENCODER's weights only)."""
+    model.flush_counters()
+    return model.model.encoder.state_dict()
 
 
 def train_pcrlv2(args, data_loader, out_channel=3):
-    distributed = int(os.environ.get("WORLD_SIZE", "1")) > 1
-    # a group this call creates is this call's to take down (see train_3d.train_pcrlv2_3d)
-    owns_group = distributed and not (torch.distributed.is_available() and torch.distributed.is_initialized())
-    ok = False
-    try:
-        model = _train_pcrlv2(args, data_loader, distributed)
-        ok = True
-        return model
-    finally:
-        if owns_group:
-            _ddp.shutdown(ok)
+    return _loop.run_with_group(lambda distributed: _train_pcrlv2(args, data_loader, distributed))
 
 
 def _train_pcrlv2(args, data_loader, distributed):
-    rank = 0
-    if distributed:
-        rank, _, local_rank = _ddp.init_process_group_from_env()
-        torch.cuda.set_device(local_rank)
-    seed_everything(getattr(args, "seed", 42))
-    enc_w = getattr(args, "encoder_weights", None) or None
-    chatty = rank == 0
-    if enc_w is None and chatty:
-        print("==> warning: encoder starts from RANDOM weights (no --encoder_weights); the reference starts from ImageNet ResNet-18")
-    model = PCRLv2(encoder_weights=enc_w).cuda()
-    if getattr(args, "amp", False):
-        model.set_compute_dtype(torch.bfloat16)
-    optimizer = FusedSGD(model.parameters(), lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
-    first_epoch = 0
-    if getattr(args, "resume", None):
-        # BEFORE the data-parallel wrapper is built: its initial broadcast then carries the resumed state from rank 0 to every rank
-        ckpt = torch.load(args.resume, map_location="cpu", weights_only=False)
-        model.model.encoder.load_state_dict(ckpt["state_dict"])
-        try:
-            optimizer.load_state_dict(ckpt["optimizer"])
-        except (ValueError, KeyError) as e:       # a checkpoint of another parameter list (group / size mismatch): keep fresh momentum, say so on EVERY rank
-            print("==> [rank {}] optimizer state not restored: {}".format(rank, e))
-        first_epoch = int(ckpt.get("epoch", -1)) + 1
-    if distributed:
-        _ddp.DataParallel(model, optimizer)
-    criterion, cosine = MSELoss2d().cuda(), CosineSimilarityMean().cuda()
-    if getattr(args, "resume", None):
-        if chatty:
-            print("==> resumed the ENCODER from {} (the 2D checkpoint layout holds nothing else); continuing with epoch {}".format(args.resume, first_epoch))
-    val_every, best_total = int(getattr(args, "val_every", 0) or 0), None
-    for epoch in range(first_epoch, args.epochs + 1):
-        adjust_learning_rate(epoch, args, optimizer)
-        if chatty:
-            print("==> training...")
-        t_start = time.time()
-        train_pcrlv2_inner(args, epoch, data_loader['train'], model, optimizer, criterion, cosine, verbose=chatty)
-        if chatty:
-            print('epoch {}, total time {:.2f}'.format(epoch, time.time() - t_start))
-            if epoch % 100 == 0 or epoch == 240:     # train_2d.py:96-107: the ENCODER's weights only
-                print('==> Saving...')
-                model.flush_counters()
-                state = {'opt': args, 'state_dict': model.model.encoder.state_dict(), 'optimizer': optimizer.state_dict(), 'epoch': epoch}
-                torch.save(state, os.path.join(args.output, "{}_{}_{}_{}_{}.pt".format(args.model, args.n, args.phase, args.ratio, epoch)))
-        if val_every > 0 and (epoch + 1) % val_every == 0:      # --val_every N: held-out metrics after every N-th epoch (0: never -- the reference)
-            val = validate(model, data_loader['eval'], epoch)
-            if chatty:
-                print('Val: [{0}]\ttotal {1:.4f}\tmg {2:.4f}\tcos {3:.4f}\tlocal {4:.4f}\tmid {5:.4f}\t({6} samples)'.format(
-                    epoch, val["total"], val["mse_out"], _mean_scales(val, "cos_global"), _mean_scales(val, "cos_local"), _mean_scales(val, "mse_mid"), val["n"]))
-                sys.stdout.flush()
-                if getattr(args, "save_best", False):
-                    best_total = save_if_best(args, model, optimizer, epoch, val, best_total)
-        if _cfg.EMPTY_CACHE_PER_EPOCH:           # the reference's per-epoch empty_cache (train_3d.py:83 / train_2d.py:108); the steady-state pools are kept (ops.empty_cache)
-            torch.cuda.empty_cache() if _cfg.EMPTY_CACHE_RAW else _ops.empty_cache()
-    return model
+    criterion, cosine = MSELoss2d().cuda(), CosineSimilarityMean().cuda()       # stateless, like train_3d's: free of device, seed and group
+
+    def make_model(rank):
+        enc_w = getattr(args, "encoder_weights", None) or None
+        if enc_w is None and rank == 0:
+            print("==> warning: encoder starts from RANDOM weights (no --encoder_weights); the reference starts from ImageNet ResNet-18")
+        return PCRLv2(encoder_weights=enc_w)
+
+    task = _loop.Task(
+        make_model=make_model,
+        make_optimizer=lambda *a, **k: FusedSGD(*a, **k),
+        resume=resume_encoder,
+        resumed="==> resumed the ENCODER from {} (the 2D checkpoint layout holds nothing else); continuing with epoch {}",
+        state_dict=encoder_state,
+        epoch=lambda epoch, loader, model, optimizer, verbose: train_pcrlv2_inner(args, epoch, loader, model, optimizer, criterion, cosine, verbose=verbose),
+        validate=lambda model, loader, epoch: validate(model, loader, epoch),
+        val_text=lambda val: val_text(val, NUM_SCALES), better=lower_total)
+    return _loop.run_epochs(args, data_loader, task, distributed)[0]
 
 
 def train_pcrlv2_inner(args, epoch, train_loader, model, optimizer, criterion, cosine, verbose=True):
     """One epoch (train_2d.py:120-195).  Returns (mean cosine loss, mean restoration loss, mean local loss)."""
-    model.train()
-    meters = {k: AverageMeter() for k in ("bt", "dt", "cos", "mg", "local")}
-    tick = time.time()
-    for it, batch in enumerate(train_loader, start=1):
-        meters["dt"].update(time.time() - tick)
-        out = train_step(model, optimizer, batch, epoch, criterion, cosine)
-        n = batch[0].size(0)
-        meters["mg"].update(out[1], n)
-        meters["cos"].update(out[2], n)
-        meters["local"].update(out[4], n)
-        log_now = it % 10 == 0
-        if log_now:
-            torch.cuda.synchronize()
-        meters["bt"].update(time.time() - tick)
-        tick = time.time()
-        if log_now and verbose:
-            m = meters
-            print('Train: [{0}][{1}/{2}]\t'
-                  'BT {3:.3f} ({4:.3f})\t'
-                  'DT {5:.3f} ({6:.3f})\t'
-                  'cos_loss {7:.3f} ({8:.3f})\t'
-                  'mg loss {9:.3f} ({10:.3f})\t'
-                  'local loss {11:.3f} ({12:.3f})'.format(
-                      epoch, it, len(train_loader), m["bt"].val, m["bt"].avg, m["dt"].val, m["dt"].avg,
-                      float(m["cos"].val), float(m["cos"].avg), float(m["mg"].val), float(m["mg"].avg),
-                      float(m["local"].val), float(m["local"].avg)))
-            sys.stdout.flush()
-    return float(meters["cos"].avg), float(meters["mg"].avg), float(meters["local"].avg)
+    avg = _loop.run_epoch(epoch, train_loader, model, lambda batch: train_step(model, optimizer, batch, epoch, criterion, cosine), LOGGED, verbose)
+    return avg["cos_loss"], avg["mg loss"], avg["local loss"]

@@ -1,15 +1,12 @@
 """3D pre-training loop on the MI355X engine -- drop-in for the reference's train_3d.py.
 
 Same entry point `train_pcrlv2_3d(args, data_loader, out_channel=3)`, same `cos_loss(cosine, output1, output2)`, same loss
-assembly, LR schedule, log line, checkpoint dict and file name.  Differences, all deliberate:
+assembly, LR schedule, log line, checkpoint dict and file name.  The run, the epoch and the bracket around a step are pcrlv2_amd.loop's,
+shared with the 2D and the supervised loop; this module holds the 3D losses, metrics and checkpoint layout.  Differences, all deliberate:
 
   * compute: PCRLv23d, the losses and SGD run on hand-written gfx950 kernels (pcrlv2_amd.models / functions / optim);
-  * `--amp` (apex O1 fp16 in the reference, train_3d.py:52-53) selects bfloat16 activations / MFMA operands with float32
-    accumulation, statistics and master weights; bf16 needs no loss scaling;
-  * `nn.DataParallel` (train_3d.py:54) -> one process per GPU + RCCL all-reduce (`pcrlv2_amd.ddp`): launch under torchrun,
-    or plain `python main.py ...` for one GPU.  `--b` is the PER-PROCESS batch (the reference splits a global batch);
-  * meters hold device scalars and are read only when the log line is printed: a step does not synchronise the GPU
-    (the reference calls .item() twice and cuda.synchronize() every iteration);
+  * `--amp` (apex O1 fp16 in the reference, train_3d.py:52-53), `nn.DataParallel` (train_3d.py:54), the meters (the reference calls .item()
+    twice and cuda.synchronize() every iteration): see pcrlv2_amd/loop.py;
   * the divergence guard (train_3d.py:140-142, `loss > 1000 and epoch > 10`) is decided ON THE DEVICE by default: a flag kernel,
     MAX-all-reduced under data parallelism, consumed by the SGD kernel (parameters and momentum stay bit-unchanged when it is set) --
     epochs 11..240 run without the forward -> backward host synchronisation the reference's `if loss > 1000` implies.  A skipped
@@ -17,7 +14,7 @@ assembly, LR schedule, log line, checkpoint dict and file name.  Differences, al
     (nobody reads them: the next step starts with zero_grad); meters and the "skip the step" line are settled when the log line is
     printed.  PCRL_GUARD_SYNC=1 (or train_step(guard="sync")) restores the reference's host-side decision: the step returns None
     before zero_grad / backward / step;
-  * `--seed`, ignored by the reference (SURVEY Q5), seeds python `random` (the scale draws) and torch;
+  * `--seed` is ignored by the reference (SURVEY Q5); here it also decides the scale draws;
   * `--resume CKPT` (not in the reference, which only saves): restores model, momentum buffers and epoch from a checkpoint of
     the layout above -- written by this engine or by the reference -- and continues with the next epoch.
 """
@@ -26,20 +23,18 @@ from __future__ import print_function
 import math
 import os
 import random
-import sys
-import time
 
 import torch
 import torch.distributed as dist
 
-from . import config as _cfg
 from . import ddp as _ddp
 from . import functions as _fn
+from . import loop as _loop
 from . import ops as _ops
 from .functions import cosine_mean, mse_loss
+from .loop import seed_everything, to_gpu  # noqa: F401  (seed_everything: tools import it from here)
 from .models import PCRLv23d
 from .optim import FusedSGD
-from .utils import AverageMeter, adjust_learning_rate
 
 BETA_PERIOD = 240   # train_3d.py:136 hard-codes 240 (not args.epochs) in the deep-supervision weight; reproduced (Q2)
 
@@ -84,16 +79,7 @@ def cos_loss(cosine, output1, output2):
     return -(sim_ab + sim_ba) * 0.5, k
 
 
-def seed_everything(seed):
-    random.seed(seed)
-    torch.manual_seed(seed)
-
-
-def _to_gpu(t):
-    return t.float().cuda(non_blocking=True)
-
-
-def _fused_cos_losses(feats1, feats2, feats_loc, n, nlocal, draws=None):
+def fused_cos_losses(feats1, feats2, feats_loc, n, nlocal, draws=None):
     """The 13 cos_loss calls of train_3d.py:119-134 as ONE launch: the scales are drawn from python's `random` in the reference's
     order (global pair; then for every local view (view 1, local_i), (view 2, local_i)), the 26 cosine means and their weights
     (-1/2 per call; /(2 * nlocal) for the local group) go to pcrl_cosine_terms_*.  -> ([global term, local term] as one float32[2], first drawn
@@ -126,11 +112,11 @@ def step_losses(model, batch, epoch, criterion, cosine):
     Returns (total, restoration, global-cosine, deep-supervision, local-cosine) as device scalars."""
     view1, view2, target, _unused_gt2, local_views = batch              # gt2 is never used by the reference either (Q3)
     n = view1.size(0)
-    target = _to_gpu(target)
+    target = to_gpu(target)
     # all cosine means of the step in one launch -- pcrl_cosine_terms_* takes up to 32 terms (2 + 4 per local view: up to 7 local views; the
     # reference's loop accepts any number): beyond that the step falls back to one launch per mean, same arithmetic
     fused = getattr(cosine, "fusable", False) and FUSED_COS_LOSSES and 2 + 4 * len(local_views) <= COS_MAX_TERMS
-    view1, view2 = _to_gpu(view1), _to_gpu(view2)
+    view1, view2 = to_gpu(view1), to_gpu(view2)
     _ops.fork_views(view1.device)  # config.VIEW_STREAMS: the second view's forward (and backward) on its own stream, next to the first's
     _ops.prepack(model, view1.device)   # config.PREPACK: this step's packed / composed weight forms on the side stream, ahead of their use
     with _ops.deferred_join():     # the decoder stages' side branches (heads, deep-supervision maps) also run under the NEXT forward; joined on exit
@@ -142,7 +128,7 @@ def step_losses(model, batch, epoch, criterion, cosine):
         with _ops.view_pass(view2.device, view2):
             _out2, feats2, _ = model(view2, **fo)
         if fused:
-            loc = _ops.concat_batch([_to_gpu(v) for v in local_views])
+            loc = _ops.concat_batch([to_gpu(v) for v in local_views])
             chunked = _ddp.chunk_partition_on()       # opt-in: nn.DataParallel's literal scatter of the [6B] local-view tensor (ddp.py)
             if chunked:
                 loc = _ddp.chunk_local_inputs(loc, n, len(local_views))
@@ -152,13 +138,13 @@ def step_losses(model, batch, epoch, criterion, cosine):
                 _ops.join_side_stream()        # the heads ran on the side stream (config.FWD_BRANCH_STREAM): the exchange reads their outputs on this one
                 feats_loc = _ddp.chunk_local_features(feats_loc, n, len(local_views))
     if fused:
-        cos2, scale = _fused_cos_losses(feats1, feats2, feats_loc, n, len(local_views))
+        cos2, scale = fused_cos_losses(feats1, feats2, feats_loc, n, len(local_views))
         l_restore = criterion(out1, target)
         beta = 0.5 * (1.0 + math.cos(math.pi * epoch / BETA_PERIOD))
         total, l_deep, l_global, l_local = _fn.loss_tail(l_restore, cos2, criterion(masks1[scale], target), beta)   # one launch: the sum and beta * MSE
         return total, l_restore, l_global, l_deep, l_local
     l_global, scale = cos_loss(cosine, feats1, feats2)
-    loc = torch.cat([_to_gpu(v) for v in local_views], dim=0)
+    loc = torch.cat([to_gpu(v) for v in local_views], dim=0)
     if _ddp.chunk_partition_on():
         loc = _ddp.chunk_local_inputs(loc, n, len(local_views))
     _, feats_loc, _ = model(loc, local=True, **fo)
@@ -213,31 +199,26 @@ def train_step(model, optimizer, batch, epoch, criterion, cosine, guard=True):
     Divergence guard (epoch > 10, loss > 1000): by default decided on the device -- the returned `.skipped` flag says whether the SGD
     kernel left the parameters alone; with guard="sync" (PCRL_GUARD_SYNC=1) on the host like the reference -- None is returned before
     zero_grad / backward / step.  guard=False: no guard."""
-    begin_step()            # forward-pass numbering / parked-gradient state start clean even after a skipped or failed step
-    dev = next(model.parameters()).device
-    _ops.throttle_host(dev)      # at most config.MAX_STEPS_AHEAD steps of run-ahead (allocator footprint, see config.py)
-    with _ops.trace_range("forward"):
-        losses = step_losses(model, batch, epoch, criterion, cosine)
     flag = None
-    if guard and epoch >= GUARD_FIRST_EPOCH:
-        # the decision is taken by the ranks that share gradients: the data-parallel wrapper's group (a wrapper on a sub-group must not pull
-        # ranks outside it into this collective); without a wrapper the process decides alone
-        dp = getattr(optimizer, "data_parallel", None)
-        flag = divergence_flag(losses[0], group=getattr(dp, "group", None), collective=dp is not None and getattr(dp, "_active", False))
-        if guard == "sync" or GUARD_SYNC:
-            if bool(flag):       # device -> host read: the reference's semantics, and its synchronisation
-                print('skip the step')
-                return None
-            flag = None
-    optimizer.zero_grad()
-    with _ops.trace_range("backward"):
-        losses[0].backward(gradient=_fn.root_gradient(losses[0]))
-    optimizer.skip_flag = flag
-    with _ops.trace_range("optimizer"):
-        optimizer.step()
-    _ops.throttle_host(dev, step_done=True)
-    # first complete step of this batch shape: size the allocator's per-stream pools for the steady state, once (ops.provision_allocator)
-    _ops.provision_allocator(dev, key=("3d", tuple(batch[0].shape), len(batch[4])))
+
+    def guard_step(loss):
+        nonlocal flag
+        if guard and epoch >= GUARD_FIRST_EPOCH:
+            # the decision is taken by the ranks that share gradients: the data-parallel wrapper's group (a wrapper on a sub-group must not pull
+            # ranks outside it into this collective); without a wrapper the process decides alone
+            dp = getattr(optimizer, "data_parallel", None)
+            flag = divergence_flag(loss, group=getattr(dp, "group", None), collective=dp is not None and getattr(dp, "_active", False))
+            if guard == "sync" or GUARD_SYNC:
+                if bool(flag):       # device -> host read: the reference's semantics, and its synchronisation
+                    print('skip the step')
+                    return True
+                flag = None
+        optimizer.skip_flag = flag
+
+    losses = _loop.run_step(model, optimizer, lambda: step_losses(model, batch, epoch, criterion, cosine),
+                            ("3d", tuple(batch[0].shape), len(batch[4])), before_update=guard_step)
+    if losses is None:
+        return None
     out = StepLosses(l.detach() for l in losses)
     out.skipped = flag
     return out
@@ -251,26 +232,24 @@ def val_beta(epoch):
     return 0.5 * (1.0 + math.cos(math.pi * epoch / BETA_PERIOD))
 
 
+def mean_scales(m, name, ns=3):
+    return sum(m[name + str(k)] for k in range(ns)) / ns
+
+
 def val_total(m, epoch):
     """The expectation of the training loss (train_3d.py:135-138) over its uniform scale draws, from the ten per-scale means."""
-    mean3 = lambda name: (m[name + "0"] + m[name + "1"] + m[name + "2"]) / 3.0
-    return m["mse_out"] + mean3("cos_global") + mean3("cos_local") + val_beta(epoch) * mean3("mse_mid")
+    return m["mse_out"] + mean_scales(m, "cos_global") + mean_scales(m, "cos_local") + val_beta(epoch) * mean_scales(m, "mse_mid")
 
 
-def _val_shard(loader, group):
-    """The batches this rank evaluates.  A loader that was built for this rank (luna_pretask_loaders: a contiguous shard of the validation
-    files per rank; anything with `sharded = True`) is taken whole; a loader with `shard(rank, world)` is asked; a plain sequence of batches
-    is cut into contiguous runs."""
-    world = dist.get_world_size(group) if group is not None or (dist.is_available() and dist.is_initialized()) else 1
-    if world <= 1 or getattr(loader, "sharded", False):
-        return loader
-    rank = dist.get_rank(group)
-    if hasattr(loader, "shard"):
-        return loader.shard(rank, world)
-    if isinstance(loader, (list, tuple)):
-        n = len(loader)
-        return loader[rank * n // world:(rank + 1) * n // world]
-    raise TypeError("validate: with a process group the loader must be sharded per rank (`sharded = True`), offer shard(rank, world), or be a sequence of batches")
+def val_text(val, ns=3):
+    """The `Val:` line of both pre-training loops, after its epoch."""
+    return 'total {0:.4f}\tmg {1:.4f}\tcos {2:.4f}\tlocal {3:.4f}\tmid {4:.4f}\t({5} samples)'.format(
+        val["total"], val["mse_out"], mean_scales(val, "cos_global", ns), mean_scales(val, "cos_local", ns), mean_scales(val, "mse_mid", ns), val["n"])
+
+
+def lower_total(val, best):
+    """--save_best of both pre-training loops: `total` improves strictly."""
+    return best is None or val["total"] < best["total"]
 
 
 def validate(model, loader, epoch, group=None):
@@ -281,46 +260,23 @@ def validate(model, loader, epoch, group=None):
     sums when there is a process group of more than one rank).  The loader's augmentation generator is reset to its seed first (`reset_rng()`):
     every pass sees the same data, two passes on the same weights give bit-identical numbers.  `model.training` is not changed.
     -> {'mse_out', 'mse_mid0..2', 'cos_global0..2', 'cos_local0..2', 'total', 'n'}; sample-weighted means (a ragged last batch counts by its size)."""
-    dev = next(model.parameters()).device
-    if hasattr(loader, "reset_rng"):
-        loader.reset_rng()
-    distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
-    acc = torch.zeros(len(VAL_KEYS) + 1, dtype=torch.float64, device=dev)
-    with torch.no_grad():
-        for batch in (_val_shard(loader, group) if distributed else loader):
-            view1, view2, target, _gt2, local_views = batch
-            view1, view2, target = _to_gpu(view1), _to_gpu(view2), _to_gpu(target)
-            out1, feats1, masks1 = model.infer(view1)
-            _, feats2, _ = model.infer(view2, features_only=True)
-            loc = _ops.concat_batch([_to_gpu(v) for v in local_views])
-            _, feats_loc, _ = model.infer(loc, local=True, features_only=True)
-            _ops.val_metrics(out1, masks1, target, feats1, feats2, feats_loc, acc)
-    if distributed:
-        dist.all_reduce(acc, group=group)
-    host = acc.cpu().tolist()          # the pass's one synchronisation
+    acc = torch.zeros(len(VAL_KEYS) + 1, dtype=torch.float64, device=next(model.parameters()).device)
+
+    def per_batch(batch):
+        view1, view2, target, _gt2, local_views = batch
+        view1, view2, target = to_gpu(view1), to_gpu(view2), to_gpu(target)
+        out1, feats1, masks1 = model.infer(view1)
+        _, feats2, _ = model.infer(view2, features_only=True)
+        loc = _ops.concat_batch([to_gpu(v) for v in local_views])
+        _, feats_loc, _ = model.infer(loc, local=True, features_only=True)
+        _ops.val_metrics(out1, masks1, target, feats1, feats2, feats_loc, acc)
+
+    host = _loop.held_out_pass(loader, group, acc, per_batch)
     n = host[-1]
     out = {k: (v / n if n else float("nan")) for k, v in zip(VAL_KEYS, host)}
     out["total"] = val_total(out, epoch)
     out["n"] = int(round(n))
     return out
-
-
-def _best_checkpoint_name(args):
-    return os.path.join(args.output, "{}_{}_{}_{}_best.pt".format(args.model, args.n, args.phase, args.ratio))
-
-
-def save_if_best(args, model, optimizer, epoch, val, best):
-    """--save_best: the checkpoint layout of train_3d.py:71-82 plus 'val' (validate's dict), written whenever `total` improves strictly.
-    -> the best total so far."""
-    if best is not None and not val["total"] < best:
-        return best
-    torch.save({'opt': args, 'state_dict': model.state_dict(), 'optimizer': optimizer.state_dict(), 'epoch': epoch, 'val': dict(val)},
-               _best_checkpoint_name(args))
-    return val["total"]
-
-
-def _checkpoint_name(args, epoch):
-    return os.path.join(args.output, "{}_{}_{}_{}_{}.pt".format(args.model, args.n, args.phase, args.ratio, epoch))
 
 
 def load_checkpoint(path, model, optimizer=None):
@@ -335,113 +291,28 @@ def load_checkpoint(path, model, optimizer=None):
 
 
 def train_pcrlv2_3d(args, data_loader, out_channel=3):
-    distributed = int(os.environ.get("WORLD_SIZE", "1")) > 1
-    # a group this call creates is this call's to take down (ddp.shutdown: barrier + destroy_process_group, also when an exception propagates):
-    # nn.DataParallel (train_3d.py:54) needs no teardown, one process per GPU does -- ranks that return with the group alive abort now and then
-    owns_group = distributed and not (torch.distributed.is_available() and torch.distributed.is_initialized())
-    ok = False
-    try:
-        model = _train_pcrlv2_3d(args, data_loader, distributed)
-        ok = True
-        return model
-    finally:
-        if owns_group:
-            _ddp.shutdown(ok)
+    return _loop.run_with_group(lambda distributed: _train_pcrlv2_3d(args, data_loader, distributed))
 
 
 def _train_pcrlv2_3d(args, data_loader, distributed):
-    rank = 0
-    if distributed:
-        rank, _, local_rank = _ddp.init_process_group_from_env()
-        torch.cuda.set_device(local_rank)
-    seed_everything(getattr(args, "seed", 42))
-    model = PCRLv23d().cuda()
-    if getattr(args, "amp", False):
-        model.set_compute_dtype(torch.bfloat16)
-    optimizer = FusedSGD(model.parameters(), lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
-    chatty = rank == 0
-    first_epoch = 0
-    if getattr(args, "resume", None):       # before the data-parallel wrapper: its initial broadcast carries rank 0's resumed state to every rank
-        first_epoch = load_checkpoint(args.resume, model, optimizer) + 1
-        if chatty:
-            print("==> resumed from {} (continuing with epoch {})".format(args.resume, first_epoch))
-    if distributed:
-        _ddp.DataParallel(model, optimizer)          # hooks itself into optimizer.step()
+    # stateless objects (`.cuda()` returns self): nothing of them depends on the device, the seed or the group that run_epochs sets up after this line
     criterion, cosine = MSELoss().cuda(), CosineSimilarityMean().cuda()
-    val_every, best_total = int(getattr(args, "val_every", 0) or 0), None
+    task = _loop.Task(
+        make_model=lambda rank: PCRLv23d(),
+        make_optimizer=lambda *a, **k: FusedSGD(*a, **k),
+        resume=lambda path, model, optimizer, rank: load_checkpoint(path, model, optimizer),
+        resumed="==> resumed from {} (continuing with epoch {})",
+        state_dict=lambda model: model.state_dict(),
+        epoch=lambda epoch, loader, model, optimizer, verbose: train_pcrlv2_inner(args, epoch, loader, model, optimizer, criterion, cosine, verbose=verbose),
+        validate=lambda model, loader, epoch: validate(model, loader, epoch),
+        val_text=val_text, better=lower_total)
+    return _loop.run_epochs(args, data_loader, task, distributed)[0]
 
-    for epoch in range(first_epoch, args.epochs + 1):          # inclusive upper bound, like the reference (Q1): lr reaches 0 in the last epoch
-        adjust_learning_rate(epoch, args, optimizer)
-        if chatty:
-            print("==> training...")
-        t_start = time.time()
-        train_pcrlv2_inner(args, epoch, data_loader['train'], model, optimizer, criterion, cosine, verbose=chatty)
-        if chatty:
-            print('epoch {}, total time {:.2f}'.format(epoch, time.time() - t_start))
-            if epoch % 100 == 0 or epoch == 240:     # checkpoint cadence and layout of train_3d.py:71-82
-                print('==> Saving...')
-                torch.save({'opt': args, 'state_dict': model.state_dict(), 'optimizer': optimizer.state_dict(), 'epoch': epoch},
-                           _checkpoint_name(args, epoch))
-        if val_every > 0 and (epoch + 1) % val_every == 0:      # --val_every N: held-out metrics after every N-th epoch (0: never -- the reference)
-            val = validate(model, data_loader['eval'], epoch)
-            if chatty:
-                mean3 = lambda name: (val[name + "0"] + val[name + "1"] + val[name + "2"]) / 3.0
-                print('Val: [{0}]\ttotal {1:.4f}\tmg {2:.4f}\tcos {3:.4f}\tlocal {4:.4f}\tmid {5:.4f}\t({6} samples)'.format(
-                    epoch, val["total"], val["mse_out"], mean3("cos_global"), mean3("cos_local"), mean3("mse_mid"), val["n"]))
-                sys.stdout.flush()
-                if getattr(args, "save_best", False):
-                    best_total = save_if_best(args, model, optimizer, epoch, val, best_total)
-        if _cfg.EMPTY_CACHE_PER_EPOCH:           # the reference's per-epoch empty_cache (train_3d.py:83 / train_2d.py:108); the steady-state pools are kept (ops.empty_cache)
-            torch.cuda.empty_cache() if _cfg.EMPTY_CACHE_RAW else _ops.empty_cache()
-    return model
+
+LOGGED = (("cos_loss", 2), ("mg loss", 1), ("local loss", 4))       # the log line of train_3d.py:153-170, in its order: label, index into the step's losses
 
 
 def train_pcrlv2_inner(args, epoch, train_loader, model, optimizer, criterion, cosine, verbose=True):
     """One epoch (train_3d.py:95-173).  Returns (mean restoration loss, mean local loss)."""
-    model.train()
-    meters = {k: AverageMeter() for k in ("bt", "dt", "cos", "mg", "local")}
-    skipped_flags = []
-    tick = time.time()
-    for it, batch in enumerate(train_loader, start=1):
-        meters["dt"].update(time.time() - tick)
-        out = train_step(model, optimizer, batch, epoch, criterion, cosine)
-        if out is None:         # host-side guard (PCRL_GUARD_SYNC=1): the reference's `continue`
-            continue
-        n = batch[0].size(0)
-        vals = (out[1], out[2], out[4])
-        if out.skipped is not None:
-            # guard decided on the device: a skipped step must not enter the meters (the reference `continue`s before them) -- its weight is
-            # n * (1 - skipped), a device scalar, AND its values are masked to 0 (a diverged loss is often inf / NaN: inf * 0 would poison the
-            # running sums); the "skip the step" lines are printed when the flags are read, with the log line
-            live = 1.0 - out.skipped.reshape(())
-            n = n * live
-            vals = tuple(torch.where(live > 0, v, torch.zeros_like(v)) for v in vals)
-            skipped_flags.append(out.skipped)
-        meters["mg"].update(vals[0], n)
-        meters["cos"].update(vals[1], n)
-        meters["local"].update(vals[2], n)
-        log_now = it % 10 == 0
-        if log_now:
-            torch.cuda.synchronize()
-            if skipped_flags and verbose:
-                for _ in range(int(torch.cat(skipped_flags).sum().item())):
-                    print('skip the step')
-            skipped_flags.clear()
-        meters["bt"].update(time.time() - tick)
-        tick = time.time()
-        if log_now and verbose:
-            m = meters
-            print('Train: [{0}][{1}/{2}]\t'
-                  'BT {3:.3f} ({4:.3f})\t'
-                  'DT {5:.3f} ({6:.3f})\t'
-                  'cos_loss {7:.3f} ({8:.3f})\t'
-                  'mg loss {9:.3f} ({10:.3f})\t'
-                  'local loss {11:.3f} ({12:.3f})'.format(
-                      epoch, it, len(train_loader), m["bt"].val, m["bt"].avg, m["dt"].val, m["dt"].avg,
-                      float(m["cos"].val), float(m["cos"].avg), float(m["mg"].val), float(m["mg"].avg),
-                      float(m["local"].val), float(m["local"].avg)))
-            sys.stdout.flush()
-    if skipped_flags and verbose:       # steps skipped after the last log line of the epoch
-        for _ in range(int(torch.cat(skipped_flags).sum().item())):
-            print('skip the step')
-    return float(meters["mg"].avg), float(meters["local"].avg)
+    avg = _loop.run_epoch(epoch, train_loader, model, lambda batch: train_step(model, optimizer, batch, epoch, criterion, cosine), LOGGED, verbose)
+    return avg["mg loss"], avg["local loss"]

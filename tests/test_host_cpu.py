@@ -615,6 +615,167 @@ def test_main_py_two_ranks_cpu_stub_exits_clean_10_times_under_cpu_load(tmp_path
     assert procs[1].returncode == 0 and "OK-raised" in out1 and not any(m in out1 for m in _ABORT_MARKS), out1
 
 
+class _LoopNet(torch.nn.Module):
+    """Stand-in for PCRLv23d / PCRLv2 (`nested`: the checkpointed weights live in .model.encoder) / a classifier; writes what happens to it into `log`."""
+    n_class = 1
+
+    def __init__(self, log, nested=False):
+        super().__init__()
+        log.append("model")
+        self.log, self.nested = log, nested
+        if nested:
+            self.model = torch.nn.Module()
+            self.model.encoder = torch.nn.Module()
+            self.head = torch.nn.Parameter(torch.zeros(2))
+        self.kept.w = torch.nn.Parameter(torch.ones(3))
+
+    @property
+    def kept(self):
+        return self.model.encoder if self.nested else self
+
+    def cuda(self, *a, **k):
+        return self
+
+    def set_compute_dtype(self, dt):
+        assert dt is torch.bfloat16
+        self.log.append("amp")
+        return self
+
+    def flush_counters(self):
+        pass
+
+
+@pytest.mark.parametrize("val_every", [0, 2])
+@pytest.mark.parametrize("loop", ["3d", "2d", "classifier"])
+def test_the_three_loops_start_resume_and_validate_in_the_same_order(loop, val_every, monkeypatch, tmp_path, capsys):
+    """One two-epoch run (`--resume` from an epoch-0 checkpoint, `--epochs 2`, `--amp`) of each training loop as a rank of a data-parallel job, on
+    stand-in model / optimizer / DataParallel / epoch / validation: seed -> model -> --amp -> optimizer -> checkpoint -> DataParallel -> epochs 1, 2;
+    the wrapper (whose construction broadcasts rank 0's state) sees the checkpoint's tensors; loaders['eval'] is read by the --val_every rule (0: never
+    in pre-training, every epoch for the classifier); the `Val:` line; only the classifier also checkpoints the last epoch."""
+    from pcrlv2_amd import config, ddp, train_2d, train_3d, train_finetune
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(config, "EMPTY_CACHE_PER_EPOCH", False)
+    log = []
+    make = lambda *a, **k: _LoopNet(log, nested=loop == "2d")        # noqa: E731
+
+    class Opt(torch.optim.SGD):
+        def __init__(self, params, lr, momentum, weight_decay):
+            log.append("sgd")
+            super().__init__(params, lr=lr, momentum=momentum, weight_decay=weight_decay)
+
+    def data_parallel(model, optimizer):
+        log.append("dp")
+        log.append(("resumed", bool((model.kept.w == 7).all())))
+
+    # the checkpoint to resume from: the kept weights are all 7 (a fresh stand-in's are 1), stored epoch 0
+    net = make()
+    ckpt = str(tmp_path / "resume.pt")
+    torch.save({"state_dict": {k: torch.full_like(v, 7.0) for k, v in net.kept.state_dict().items()},
+                "optimizer": Opt(net.parameters(), 1e-3, 0.9, 1e-4).state_dict(), "epoch": 0}, ckpt)
+    del log[:]
+    real_seed, real_load = random.seed, torch.load
+    monkeypatch.setattr(random, "seed", lambda *a: (log.append("seed"), real_seed(*a))[1])
+    monkeypatch.setattr(torch, "load", lambda *a, **k: (log.append("load"), real_load(*a, **k))[1])
+    monkeypatch.setattr(torch.cuda, "set_device", lambda *a, **k: None)
+    monkeypatch.setattr(torch.distributed, "barrier", lambda *a, **k: None)
+    monkeypatch.setattr(ddp, "init_process_group_from_env", lambda *a, **k: (0, 2, 0))
+    monkeypatch.setattr(ddp, "DataParallel", data_parallel)
+
+    loaders = _EvalCountingLoaders()
+    args = types.SimpleNamespace(lr=1e-3, momentum=0.9, weight_decay=1e-4, epochs=2, output=str(tmp_path), model="pcrlv2", n="x", phase="p", ratio=0.8, seed=1,
+                                 amp=True, resume=ckpt, encoder_weights="", lr_decay_epochs=None, val_every=val_every, save_best=False)
+    if loop == "classifier":
+        T = train_finetune
+        val = {"loss": 0.25, "mean_auroc": 0.75, "auroc": [0.75], "n": 11}
+        monkeypatch.setattr(T, "train_inner", lambda a, epoch, loader, model, opt, verbose=True: log.append("epoch %d" % epoch))
+        monkeypatch.setattr(T, "evaluate", lambda model, loader, group=None: dict(val))
+        run = lambda: T._train_classifier(args, loaders, make, "stand-in", True)        # noqa: E731
+        val_line = "Val: [{}]\tloss 0.2500\tmean AUROC 0.7500\t(11 samples)"
+    else:
+        T = train_3d if loop == "3d" else train_2d
+        val = dict({k: 0.125 for k in T.VAL_KEYS}, total=0.5, n=11)
+        monkeypatch.setattr(T, "PCRLv23d" if loop == "3d" else "PCRLv2", make)
+        monkeypatch.setattr(T, "train_pcrlv2_inner", lambda a, epoch, loader, model, opt, crit, cos, verbose=True: log.append("epoch %d" % epoch))
+        monkeypatch.setattr(T, "validate", lambda model, loader, epoch, group=None: dict(val))
+        run = lambda: (T._train_pcrlv2_3d if loop == "3d" else T._train_pcrlv2)(args, loaders, True)        # noqa: E731
+        val_line = "Val: [{}]\ttotal 0.5000\tmg 0.1250\tcos 0.1250\tlocal 0.1250\tmid 0.1250\t(11 samples)"
+    monkeypatch.setattr(T, "FusedSGD", Opt)
+    run()
+    assert log == ["seed", "model", "amp", "sgd", "load", "dp", ("resumed", True), "epoch 1", "epoch 2"], log
+    validated = [1, 2] if loop == "classifier" and val_every == 0 else [1] if val_every == 2 else []
+    assert loaders.eval_reads == len(validated)
+    out = capsys.readouterr().out.splitlines()
+    assert [ln for ln in out if ln.startswith("Val: [")] == [val_line.format(e) for e in validated]
+    assert [ln for ln in out if ln.startswith("==> resumed")] == [
+        {"3d": "==> resumed from {} (continuing with epoch 1)", "2d": "==> resumed the ENCODER from {} (the 2D checkpoint layout holds nothing else); continuing with epoch 1",
+         "classifier": "==> resumed the classifier from {}; continuing with epoch 1"}[loop].format(ckpt)]
+    assert sorted(f for f in os.listdir(tmp_path) if f != "resume.pt") == (["pcrlv2_x_p_0.8_2.pt"] if loop == "classifier" else [])
+
+
+EPOCH_LINES = """\
+skip the step
+Train: [11][10/25]\tcos_loss 18.125 (8.725)\tmg loss 9.125 (4.425)\tlocal loss 36.125 (17.325)
+skip the step
+Train: [11][20/25]\tcos_loss 38.125 (19.985)\tmg loss 19.125 (10.055)\tlocal loss 76.125 (39.846)
+skip the step
+(12.086538314819336, 47.971153259277344)
+(12.086538314819336, 47.971153259277344)
+Train: [3][10/25]\tcos_loss 18.250 (9.450)\tmg loss 9.250 (4.850)\tlocal loss 36.250 (18.650)
+Train: [3][20/25]\tcos_loss 38.250 (19.450)\tmg loss 19.250 (9.850)\tlocal loss 76.250 (38.650)
+(24.25, 12.25, 48.25)
+Train: [2][10/25]\tbce loss 4.500 (2.300)
+Train: [2][20/25]\tbce loss 9.500 (4.800)
+6.0
+"""
+
+
+def test_epoch_loops_meter_and_print_as_before(monkeypatch, capsys):
+    """One epoch of each loop on stand-in steps over 25 batches of 2 or 3 samples: the `Train:` line every tenth iteration, its BT / DT fields, the
+    loops' return values; for the 3D loop a step that returned None (batch 4: not metered), steps whose `.skipped` flag is set (batches 7 -- with inf
+    losses --, 12 and 23: weight 0, values masked, one `skip the step` line each, printed with the next log line or at the end of the epoch) or clear,
+    and nothing printed with verbose=False.  EPOCH_LINES is what the three loops printed before they shared one epoch loop."""
+    import re
+    from pcrlv2_amd import train_2d as T2, train_3d as T3, train_finetune as TF
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+
+    class Net(torch.nn.Module):
+        pass
+
+    def step3(model, opt, batch, epoch, crit, cos, guard=True):
+        i = batch[1]
+        if i == 4:
+            return None
+        out = T3.StepLosses(torch.tensor(float(i) * k + 0.125) if i != 7 else torch.tensor(float("inf")) for k in range(5))
+        if i >= 5:
+            out.skipped = torch.tensor([1.0 if i in (7, 12, 23) else 0.0])
+        return out
+
+    monkeypatch.setattr(T3, "train_step", step3)
+    monkeypatch.setattr(T2, "train_step", lambda model, opt, batch, epoch, crit, cos: tuple(torch.tensor(float(batch[1]) * k + 0.25) for k in range(5)))
+    monkeypatch.setattr(TF, "train_step", lambda model, opt, batch: (torch.tensor(float(batch[1]) * 0.5), None))
+    loader = [(torch.zeros(3 if i % 2 else 2, 1), i) for i in range(25)]
+    print(T3.train_pcrlv2_inner(None, 11, loader, Net(), None, None, None))
+    print(T3.train_pcrlv2_inner(None, 11, loader, Net(), None, None, None, verbose=False))
+    print(T2.train_pcrlv2_inner(None, 3, loader, Net(), None, None, None))
+    print(TF.train_inner(None, 2, loader, Net(), None))
+    out = capsys.readouterr().out
+    timing = r"\tBT \d+\.\d{3} \(\d+\.\d{3}\)\tDT \d+\.\d{3} \(\d+\.\d{3}\)\t"
+    assert len(re.findall(r"^Train: \[\d+\]\[\d+/25\]" + timing, out, flags=re.M)) == 6
+    assert re.sub(timing, "\t", out) == EPOCH_LINES
+
+
+class _EvalCountingLoaders(dict):
+    """{'train', 'eval', 'test'} that counts the reads of 'eval'."""
+
+    def __init__(self):
+        super().__init__(train=[0, 1], eval="EVAL", test="TEST")
+        self.eval_reads = 0
+
+    def __getitem__(self, k):
+        self.eval_reads += k == "eval"
+        return super().__getitem__(k)
+
+
 @pytest.mark.parametrize("tag", ["loss2d_b4_5scales", "loss2d_b2_nl3"])
 def test_2d_loss_assembly_and_draw_order_match_the_reference(tag, golden_dir, monkeypatch):
     """What can be pinned of the 2D path without smp / torchvision: pcrlv2_amd.train_2d's `cos_loss` and loss assembly against

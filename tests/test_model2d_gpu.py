@@ -417,7 +417,7 @@ def test_fused_cosine_terms_and_loss_tail_match_the_reference_cos_loss_2d(tag):
     import numpy as np
     import pcrlv2_2d_oracle as O2
     from pcrlv2_amd import functions as Fn, train_2d
-    from pcrlv2_amd.train_3d import _fused_cos_losses
+    from pcrlv2_amd.train_3d import fused_cos_losses
     fx = np.load(os.path.join(os.path.dirname(__file__), "golden", tag + ".npz"))
     b, nl, epoch = int(fx["b"]), int(fx["nlocal"]), int(fx["epoch"])
     f1, f2, fl, mask1, masks1, gt = O2.fill_loss_inputs(b, nl, dtype=torch.float64)
@@ -434,7 +434,7 @@ def test_fused_cosine_terms_and_loss_tail_match_the_reference_cos_loss_2d(tag):
     random.seed(int(fx["seed"]))
     draws = [random.randint(0, len(f1) - 1) for _ in range(1 + 2 * nl)]
     assert draws == [int(v) for v in fx["draws"]]
-    cos2, k0 = _fused_cos_losses(g1, g2, gl, b, nl, draws=draws)
+    cos2, k0 = fused_cos_losses(g1, g2, gl, b, nl, draws=draws)
     assert k0 == int(fx["index2"])
     l1 = Fn.mse_loss(dev(mask1), dev(gt))
     l4raw = Fn.mse_loss(dev(masks1[k0]), dev(gt))
