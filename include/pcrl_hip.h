@@ -745,6 +745,33 @@ int pcrl_cls_head_bwd(const float* probs, const uint8_t* labels, const float* dl
                       const float* w, void* da, float* dw, float* db, int N, int H, int W, int C, int K, int dtype, pcrl_stream_t stream);
 int pcrl_auroc_counts(const float* probs, const uint8_t* labels, int64_t* counts, int64_t M, int K, pcrl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * 3D path, segmentation fine-tuning (csrc/seg_head.hip).
+ * pcrl_seg_head_fwd / _bwd / _eval -- out_tr.final_conv (1x1x1, 64 -> K) -> sigmoid -> wb * BCE + wd * (1 - mean_k Dice_k) as one operator.  Replaces,
+ *   per class, pcrl_conv3d_to1_fwd + pcrl_sigmoid_fwd (forward) and pcrl_sigmoid_bwd + pcrl_conv3d_to1_wgrad + pcrl_conv3d_to1_dgrad (backward) of the
+ *   n_class != 1 constructor variant, and the aten loss passes over [N, K, D, H, W] that a segmentation loss on top of them would add.
+ *   a: `dtype` NDHWC rows [N * S][64] (S = D * H * W voxels per sample); w float32 [K][64], b float32 [K], 1 <= K <= 7; labels uint8 [N * S]: bit k = the
+ *   voxel belongs to class k (classes may overlap), bit 7 = the voxel is NOT counted (no sum, zero gradient).
+ *   BCE = mean over the Mc counted voxels x K of max(z,0) - y z + log1p(exp(-|z|)) (0 when Mc = 0); Dice_k = (2 I_k + 1) / (P_k + G_k + 1) with
+ *   I = sum p g, P = sum p, G = sum g over the counted voxels of the whole call.
+ *   forward : sums float64 [4 K + 1] = {I_k, P_k, G_k, BCE_k} per class, then Mc; loss float32 [1].  One read of a; per-block float64 partials and a
+ *             fixed-order second launch (deterministic; no floating-point atomics); no [M][K] tensor is written.
+ *   backward: from dloss[0] and the forward's sums (both on the device) -- recomputes z and p with the forward's arithmetic; dx `dtype` [N * S][64] written
+ *             once (NULL: not wanted; rows of uncounted voxels are exactly zero, and their activations enter neither dw nor any sum, finite or not), dw float32 [K][64], db float32 [K] from per-block partials added in
+ *             block order.
+ *   eval    : the forward (labels may be NULL: nothing labelled, everything counted) plus counts[case_index[n]][k] += {TP, |pred|, |gt|} (int64
+ *             [n_cases][K][3], NOT cleared here; 64-bit integer atomics, order-independent) with pred = (z >= 0); case_index int32 [N] or NULL (= n),
+ *             an index outside [0, n_cases) is skipped; mask uint8 [N * S] or NULL: the predicted bitmask, 0 where bit 7 of the label is set.
+ *   ws: pcrl_seg_head_ws_bytes(N, S, K) bytes for any of the three. */
+size_t pcrl_seg_head_ws_bytes(int N, int64_t S, int K);
+int pcrl_seg_head_fwd(const void* a, const float* w, const float* b, const uint8_t* labels, double* sums, float* loss, float wb, float wd, void* ws,
+                      size_t ws_bytes, int N, int64_t S, int K, int dtype, pcrl_stream_t stream);
+int pcrl_seg_head_bwd(const void* a, const float* w, const float* b, const uint8_t* labels, const double* sums, const float* dloss, float wb, float wd,
+                      void* dx, float* dw, float* db, void* ws, size_t ws_bytes, int N, int64_t S, int K, int dtype, pcrl_stream_t stream);
+int pcrl_seg_head_eval(const void* a, const float* w, const float* b, const uint8_t* labels, const int* case_index, int64_t* counts, int n_cases,
+                       uint8_t* mask, double* sums, float* loss, float wb, float wd, void* ws, size_t ws_bytes, int N, int64_t S, int K, int dtype,
+                       pcrl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -520,6 +520,98 @@ class OutFn(Function):
         return out
 
 
+class UpConvsFn(Function):
+    """The convolutions of an UpTransition alone -- up_conv -> ops.0 -> ops.1 (models/pcrlv2_model_3d.py:63-66) -- for the segmentation fine-tuning
+    forward (models.Segmenter3d.loss), which runs neither the projection / predictor heads nor the deep-supervision head: their parameters and running
+    statistics are not touched.  The same ops.* calls as UpStageFn makes for these three layers, in the same order (ops.1 without the fused
+    global average pool, which only the heads consume).
+
+    inputs : x, up_w, up_b, [w,b,gamma,beta] of ops.0, ops.1, module
+    output : the stage's activation"""
+
+    @staticmethod
+    def forward(ctx, x, up_w, up_b, w0, b0, g0, be0, w1, b1, g1, be1, mod):
+        dt = mod.compute_dtype
+        x = ops.to_act(x, dt)
+        l0, l1 = mod.ops[0], mod.ops[1]
+        gn = getattr(l0, "_gn_groups", 0)
+        rs = lambda m: (None, None) if gn else (m.bn1.running_mean, m.bn1.running_var)
+        s0, s1 = _slope(l0), _slope(l1)
+        if config.COMPOSE_UPCONV and not gn and s0 is None:
+            a0, sv0 = ops.upconv_luconv_forward(x, up_w, up_b, w0, b0, g0, be0, *rs(l0), mod._composed_up, l0._act, dt)
+        else:
+            up = ops.convt_forward(x, up_w, up_b, mod._packed_up, dt)
+            a0, sv0 = ops.luconv_forward(up, w0, b0, g0, be0, *rs(l0), l0._packed, l0._act, dt, gn_groups=gn, prelu=s0)
+        a1, sv1 = ops.luconv_forward(a0, w1, b1, g1, be1, *rs(l1), l1._packed, l1._act, dt, gn_groups=gn, prelu=s1)
+        for m in (l0, l1):
+            m._count_batch()
+        ctx.mod, ctx.dt, ctx.x, ctx.sv0, ctx.sv1 = mod, dt, x, sv0, sv1
+        ctx.pass_idx = getattr(mod, "_pass_idx", 1)
+        ctx.plist = (up_w, up_b, w0, b0, g0, be0, w1, b1, g1, be1)
+        ctx.set_materialize_grads(False)
+        return a1
+
+    @staticmethod
+    def backward(ctx, d_out):
+        if d_out is None:
+            return (None,) * 12
+        mod, dt = ctx.mod, ctx.dt
+        up_w, up_b, w0, b0, g0, _, w1, _, g1, _ = ctx.plist
+        l0, l1 = mod.ops[0], mod.ops[1]
+        d_a0, gw1, gb1, gg1, gbe1 = ops.luconv_backward(ctx.sv1, _act_grad(d_out, dt), w1, g1, l1._packed, dt, need_dx=True, bnred=ctx.sv0)
+        _park_slope(l1, ctx.sv1)
+        deferred = ()
+        if ctx.sv0.kind == "upc":     # composed up_conv + conv1, as in UpStageFn.backward
+            defer = config.DIRECT_PARAM_GRADS
+            dx, g_upw, g_upb, gw0, gb0, gg0, gbe0 = ops.upconv_luconv_backward(ctx.sv0, d_a0, up_w, up_b, w0, b0, g0, mod._composed_up, dt,
+                                                                               need_dx=ctx.needs_input_grad[0], defer=defer)
+            if defer:
+                deferred = (0, 1, 2)
+                _queue_end_of_backward()
+                if getattr(ctx, "pass_idx", 1) == 0 and (config.EARLY_COMPOSED or _final_callback is not None):
+                    _deliver_composed(mod._composed_up)
+        else:
+            g_upb = torch.empty(up_w.shape[1], dtype=torch.float32, device=d_a0.device)
+            d_up, gw0, gb0, gg0, gbe0 = ops.luconv_backward(ctx.sv0, d_a0, w0, g0, l0._packed, dt, need_dx=True, dx_colsum=g_upb)
+            _park_slope(l0, ctx.sv0)
+            dx, g_upw, g_upb = ops.convt_backward(ctx.x, d_up, up_w, mod._packed_up, dt, need_dx=ctx.needs_input_grad[0], db=g_upb)
+        grads = [g_upw, g_upb, gw0, gb0, gg0, gbe0, gw1, gb1, gg1, gbe1]
+        out = (dx,) + tuple(_park(p, g) for p, g in zip(ctx.plist, grads)) + (None,)
+        mark_final(ctx, [p for k, p in enumerate(ctx.plist) if k not in deferred])
+        return out
+
+
+class SegHeadFn(Function):
+    """wb * BCE + wd * (1 - mean Dice) of sigmoid(out_tr.final_conv(a)) against a uint8 bitmask -- the segmentation head and its loss as ONE node on
+    pcrl_seg_head_fwd / _bwd (csrc/seg_head.hip): the activation is read once forward and once backward, no [N,K,D,H,W] tensor exists.
+    -> (loss 0-d float32, sums float64 [4 K + 1] (no gradient): {I, P, G, BCE} per class and the counted voxels, for logging)."""
+
+    @staticmethod
+    def forward(ctx, a, w, b, labels, wb, wd, mod):
+        dt = mod.compute_dtype
+        a = ops.to_act(a, dt)
+        loss, sums = ops.seg_head_forward(a, w, b, labels, dt, wb, wd)
+        ctx.a, ctx.dt, ctx.labels, ctx.wts = a, dt, labels, (wb, wd)     # `a` is an INPUT (no reference cycle)
+        ctx.plist = (w, b)
+        ctx.pass_idx = getattr(mod, "_pass_idx", 1)
+        ctx.save_for_backward(sums)          # an OUTPUT needed in backward: never stashed on ctx directly
+        ctx.mark_non_differentiable(sums)
+        ctx.set_materialize_grads(False)
+        return loss, sums
+
+    @staticmethod
+    def backward(ctx, dloss, _dsums):
+        if dloss is None:
+            return (None,) * 7
+        w, b = ctx.plist
+        (sums,) = ctx.saved_tensors
+        dx, dw, db = ops.seg_head_backward(ctx.a, w, b, ctx.labels, sums, dloss, ctx.dt, *ctx.wts, need_dx=ctx.needs_input_grad[0])
+        out = dx, _park(w, dw.view(w.shape)), _park(b, db), None, None, None, None
+        mark_final(ctx, ctx.plist)
+        ctx.a = ctx.labels = None
+        return out
+
+
 class TrilinearFn(Function):
     """F.interpolate(x, scale_factor=s, mode='trilinear')  --  models/pcrlv2_model_3d.py:125-126."""
 

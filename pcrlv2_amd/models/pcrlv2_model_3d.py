@@ -517,3 +517,116 @@ class NoduleClassifier(nn.Module):
             return self._forward_eval(x)
         labels = torch.zeros((x.shape[0], self.n_class), dtype=torch.uint8, device=x.device)
         return self.loss(x, labels)[1]
+
+
+class Segmenter3d(PCRLv23d):
+    """The downstream model of the whole pre-trained 3D network, decoder included: voxel-wise segmentation (BraTS / LiTS in the paper; the reference's
+    README loads the whole PCRLv23d for it, its fine-tune branch is not public).  It IS a PCRLv23d(n_class, in_channels): the same modules under the
+    same names, so `state_dict()` has the 169 keys of a pre-training checkpoint and a fine-tuned one loads into the reference's
+    PCRLv23d(n_class=K, in_channels=C).  `weights`: a 3D pre-training checkpoint (load_pretrained).
+
+    loss(x, labels) is the training step's path: the encoder half of the training forward, each decoder stage as up_conv -> ops.0 -> ops.1 only
+    (functions.UpConvsFn), then the output head and the Dice/BCE loss as one operator (functions.SegHeadFn, csrc/seg_head.hip).  The projection,
+    predictor and deep-supervision heads are NOT run: their parameters have requires_grad = False here and their running statistics and counters do
+    not move; `trainable_parameters()` is what the optimiser gets.  infer(x, ...) is the eval-mode forward on the inference kernels followed by
+    pcrl_seg_head_eval.  labels: uint8 [N, D, H, W], bit k = class k (classes may overlap), bit 7 = the voxel is not counted."""
+
+    _HEADS = ("bn.", "predictor_head.", "deep_supervision_head.")
+
+    def __init__(self, n_class, in_channels=1, weights=None, act='relu', norm='bn', wb=1.0, wd=1.0):
+        if not 1 <= int(n_class) <= 7:
+            raise ValueError("n_class must be in 1..7 (one bit of the label byte per class; bit 7 means 'not counted'), got %r" % (n_class,))
+        super().__init__(n_class=int(n_class), act=act, norm=norm, in_channels=in_channels)
+        self.n_class, self.in_channels, self.wb, self.wd = int(n_class), int(in_channels), float(wb), float(wd)
+        for name, p in self.named_parameters():
+            if self._is_head(name):
+                p.requires_grad_(False)
+        if weights is not None:
+            self.load_pretrained(weights)
+
+    @classmethod
+    def _is_head(cls, key):
+        parts = key.split(".", 1)
+        return parts[0].startswith("up_tr") and len(parts) > 1 and parts[1].startswith(cls._HEADS)
+
+    def trainable_parameters(self):
+        """The parameters loss() reaches, in registration order."""
+        return [p for p in self.parameters() if p.requires_grad]
+
+    def load_pretrained(self, path):
+        """A 3D pre-training checkpoint's 'state_dict', strictly, with two announced exceptions that keep their fresh initialisation:
+        `out_tr.final_conv.*` when n_class != the checkpoint's, `down_tr64.ops.0.conv1.weight` when in_channels differs.  Any other missing,
+        unexpected or mis-shaped key raises KeyError."""
+        ckpt = torch.load(path, map_location="cpu", weights_only=False)
+        if not isinstance(ckpt, dict) or "state_dict" not in ckpt:
+            raise KeyError(f"{path}: no 'state_dict' entry (a 3D pre-training checkpoint is expected)")
+        strip = lambda k: k[len("module."):] if k.startswith("module.") else k      # noqa: E731
+        sd = {strip(k): v for k, v in ckpt["state_dict"].items()}
+        own = self.state_dict()
+        if set(sd) != set(own):
+            raise KeyError(f"{path}: keys differ from the model's: missing {sorted(set(own) - set(sd))[:4]}, unexpected {sorted(set(sd) - set(own))[:4]}")
+        may_differ = {"out_tr.final_conv.weight": "n_class", "out_tr.final_conv.bias": "n_class", "down_tr64.ops.0.conv1.weight": "in_channels"}
+        for k in list(sd):
+            if tuple(sd[k].shape) != tuple(own[k].shape):
+                if k not in may_differ:
+                    raise KeyError(f"{path}: {k} has shape {tuple(sd[k].shape)}, the model's is {tuple(own[k].shape)}")
+                print(f"==> {k}: checkpoint {tuple(sd[k].shape)} != model {tuple(own[k].shape)} ({may_differ[k]} differs): freshly initialised")
+                sd[k] = own[k]
+        self.load_state_dict(sd)
+
+    def _check(self, x, labels):
+        if not x.is_cuda:
+            raise RuntimeError("Segmenter3d (pcrlv2_amd) runs on the GPU only: input is on %s and there is no CPU fallback" % x.device)
+        if x.dim() != 5 or x.shape[1] != self.in_channels or any(int(s) % 8 for s in x.shape[2:]):
+            raise ValueError(f"Segmenter3d: input must be [N, {self.in_channels}, D, H, W] with D, H, W multiples of 8, got {tuple(x.shape)}")
+        if labels is not None and (labels.dtype != torch.uint8 or tuple(labels.shape) != (x.shape[0],) + tuple(x.shape[2:])):
+            raise ValueError(f"Segmenter3d: labels must be a uint8 bitmask of shape {(x.shape[0],) + tuple(x.shape[2:])}, got {labels.dtype} {tuple(labels.shape)}")
+
+    def forward(self, x, *args, **kwargs):
+        raise RuntimeError("Segmenter3d has no forward(): PCRLv23d's would run the pre-training heads, which are frozen here.  Call loss(x, labels) in "
+                           "training and infer(x, ...) for evaluation; the pre-training forward of these weights is PCRLv23d(n_class, in_channels)'s")
+
+    def features(self, x):
+        """Training mode: the last decoder stage's activation [N, 64, D, H, W] (NDHWC memory) -- the encoder half of the training forward, then each
+        decoder stage without its heads.  One forward pass of the step (ops.next_pass)."""
+        pass_idx = ops.next_pass()
+        mods = self._stage_modules()
+
+        def mine():
+            for m in mods:
+                m._pass_idx = pass_idx
+
+        lu = lambda m: (m.conv1.weight, m.conv1.bias, m.bn1.weight, m.bn1.bias)      # noqa: E731
+        h = _train_encoder(self, x, mine, lazy_skips=True, stash=False)
+        for name, _, _ in _DECODER:
+            mine()
+            up = getattr(self, name)
+            h = Fn.UpConvsFn.apply(h, up.up_conv.weight, up.up_conv.bias, *lu(up.ops[0]), *lu(up.ops[1]), up)
+        mine()
+        return h
+
+    def loss(self, x, labels):
+        """Training mode: -> (loss 0-d, sums float64 [4 K + 1] (no gradient): {I, P, G, BCE} per class, then the counted voxels)."""
+        self._check(x, labels)
+        if not self.training:
+            raise RuntimeError("Segmenter3d.loss is the TRAINING step's path; in eval mode call infer")
+        fc = self.out_tr.final_conv
+        out = Fn.SegHeadFn.apply(self.features(x), fc.weight, fc.bias, labels.contiguous(), self.wb, self.wd, self.out_tr)
+        ops.end_of_forward_join()
+        return out
+
+    @torch.no_grad()
+    def infer(self, x, labels=None, case_index=None, counts=None, want_mask=False):
+        """The eval-mode forward on the inference kernels, whatever `self.training` says; nothing of the model is touched.  Prediction: z_k >= 0.
+        counts int64 [cases, K, 3] (device) gets {TP, |pred|, |gt|} of sample n added at row case_index[n] (int32 [N]; None: row n of a fresh table).
+        -> (counts, loss 0-d, sums float64 [4 K + 1], predicted bitmask uint8 [N, D, H, W] | None)"""
+        self._check(x, labels)
+        dt = self.compute_dtype
+        h = _eval_encoder(self, x, dt, True, stash=False)
+        for name, _, _ in _DECODER:
+            up = getattr(self, name)
+            h = ops.convt_forward(ops.to_act(h, dt), up.up_conv.weight, up.up_conv.bias, up._packed_up, dt)
+            h = _eval_luconv(up.ops[1], _eval_luconv(up.ops[0], h, dt, True), dt, True)
+        fc = self.out_tr.final_conv
+        return ops.seg_head_eval(ops.to_act(h, dt), fc.weight, fc.bias, dt, labels=None if labels is None else labels.contiguous(),
+                                 case_index=case_index, counts=counts, want_mask=want_mask, wb=self.wb, wd=self.wd)

@@ -1636,3 +1636,68 @@ def gn_backward_rows(da, saved, gamma, groups, act, dtype):
                dtype_code(dtype), s)
     return dy, dg_n.view(N, C).sum(0), db_n.view(N, C).sum(0)
 
+
+
+# ----------------------------------------------------------------------------------------------
+# segmentation fine-tuning: out_tr.final_conv + sigmoid + Dice/BCE as one operator (csrc/seg_head.hip)
+# ----------------------------------------------------------------------------------------------
+def _seg_args(a, w, b, labels, dtype, what):
+    N, D, H, W, C = dims(a)
+    K = w.shape[0]
+    if a.dtype != dtype or C != 64 or w.numel() != K * 64 or w.dtype != torch.float32 or b.dtype != torch.float32 or b.numel() != K:
+        raise PcrlError(f"{what}: activation {a.dtype} with {C} channels against a {tuple(w.shape)} {w.dtype} weight in {dtype} (64 channels are expected)")
+    S = D * H * W
+    if labels is not None and (labels.dtype != torch.uint8 or labels.numel() != N * S or not labels.is_contiguous() or labels.device != a.device):
+        raise PcrlError(f"{what}: labels must be a contiguous uint8 bitmask of {N * S} voxels on {a.device}, got {labels.dtype} {tuple(labels.shape)}")
+    return N, S, K, w.detach().reshape(K, 64).contiguous(), b.detach().contiguous()
+
+
+def _seg_ws(N, S, K, device):
+    nb = lib().call("pcrl_seg_head_ws_bytes", N, S, K)
+    return workspace(nb, device), nb
+
+
+def seg_head_forward(a, w, b, labels, dtype, wb=1.0, wd=1.0):
+    """wb * BCE + wd * (1 - mean_k Dice_k) of sigmoid(final_conv(a)) against the uint8 bitmask `labels` [N,D,H,W] (bit k: class k, bit 7: not counted),
+    one operator (pcrl_seg_head_fwd).  -> (loss 0-d float32, sums float64 [4 K + 1]: {I, P, G, BCE} per class, then the counted voxels)"""
+    N, S, K, wc, bc = _seg_args(a, w, b, labels, dtype, "seg_head_forward")
+    sums = torch.empty(4 * K + 1, dtype=torch.float64, device=a.device)
+    loss = _f32(1, a.device)
+    ws, nb = _seg_ws(N, S, K, a.device)
+    lib().call("pcrl_seg_head_fwd", a, wc, bc, labels, sums, loss, wb, wd, ws, nb, N, S, K, dtype_code(dtype), stream_handle())
+    return loss.view(()), sums
+
+
+def seg_head_backward(a, w, b, labels, sums, dloss, dtype, wb=1.0, wd=1.0, need_dx=True):
+    """Backward of seg_head_forward from d loss and the forward's `sums`, both on the device (pcrl_seg_head_bwd: z and p are recomputed).
+    -> (dx like `a` | None, dw float32 [K,64], db float32 [K])"""
+    N, S, K, wc, bc = _seg_args(a, w, b, labels, dtype, "seg_head_backward")
+    dx = torch.empty_like(a) if need_dx else None
+    dw, db = _f32(K * 64, a.device).view(K, 64), _f32(K, a.device)
+    ws, nb = _seg_ws(N, S, K, a.device)
+    lib().call("pcrl_seg_head_bwd", a, wc, bc, labels, sums, dloss.detach().reshape(1).float(), wb, wd, dx, dw, db, ws, nb, N, S, K, dtype_code(dtype),
+               stream_handle())
+    return dx, dw, db
+
+
+def seg_head_eval(a, w, b, dtype, labels=None, case_index=None, counts=None, want_mask=False, wb=1.0, wd=1.0):
+    """The inference sibling (pcrl_seg_head_eval): prediction z_k >= 0; `counts` int64 [cases, K, 3] on the device gets {TP, |pred|, |gt|} of sample n ADDED
+    at row case_index[n] (int32 [N] on the device; None: row n; counts None: a fresh zeroed [N, K, 3]).  labels None: nothing labelled, every voxel counted.
+    -> (counts, loss 0-d float32, sums float64 [4 K + 1], mask uint8 [N,D,H,W] | None)"""
+    N, S, K, wc, bc = _seg_args(a, w, b, labels, dtype, "seg_head_eval")
+    if counts is None:
+        counts = torch.zeros((N, K, 3), dtype=torch.int64, device=a.device)
+    if counts.dtype != torch.int64 or counts.dim() != 3 or tuple(counts.shape[1:]) != (K, 3) or not counts.is_contiguous() or counts.device != a.device:
+        raise PcrlError(f"seg_head_eval: counts must be a contiguous int64 [cases, {K}, 3] tensor on {a.device}, got {counts.dtype} {tuple(counts.shape)}")
+    if case_index is not None and (case_index.dtype != torch.int32 or case_index.numel() != N or not case_index.is_contiguous() or case_index.device != a.device):
+        raise PcrlError(f"seg_head_eval: case_index must be a contiguous int32 [{N}] tensor on {a.device}")
+    if case_index is None and counts.shape[0] < N:
+        raise PcrlError(f"seg_head_eval: counts has {counts.shape[0]} rows for {N} samples and no case_index")
+    _, D, H, W, _ = dims(a)
+    mask = torch.empty((N, D, H, W), dtype=torch.uint8, device=a.device) if want_mask else None
+    sums = torch.empty(4 * K + 1, dtype=torch.float64, device=a.device)
+    loss = _f32(1, a.device)
+    ws, nb = _seg_ws(N, S, K, a.device)
+    lib().call("pcrl_seg_head_eval", a, wc, bc, labels, case_index, counts, counts.shape[0], mask, sums, loss, wb, wd, ws, nb, N, S, K, dtype_code(dtype),
+               stream_handle())
+    return counts, loss.view(()), sums, mask

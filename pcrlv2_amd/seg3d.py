@@ -1,0 +1,91 @@
+"""3D segmentation on the pre-trained PCRLv2 network, decoder included: fine-tuning and prediction.
+
+    python seg3d.py train   --data DIR --phase finetune --weights PRETRAIN.pt --n_class 3 --in_channels 4 --save_best --output OUT
+    python seg3d.py predict --data DIR --list test.txt --weights OUT/pcrlv2_seg3d_finetune_1.0_best.pt --out PRED
+
+DIR holds <case>_img.npy [C,X,Y,Z] float32 / float16, <case>_seg.npy [X,Y,Z] uint8 (bit k = class k, bit 7 = not counted) and train.txt / val.txt /
+test.txt (pcrlv2_amd/data_seg.py); `--data synthetic` trains on phantoms.  The loop is pcrlv2_amd/train_seg.py, the model models.Segmenter3d, the
+output head and its Dice/BCE loss one HIP operator (csrc/seg_head.hip).  DESIGN.md section 15.
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+
+
+def check_train(args):
+    """Every refused combination exits with its message, before anything touches a GPU."""
+    from .data_seg import check_n_class, parse_crop
+    check_n_class(args.n_class)
+    parse_crop(args.crop)
+    if args.in_channels < 1:
+        raise SystemExit(f"--in_channels {args.in_channels}: at least 1")
+    if args.phase == "finetune" and not args.weights:
+        raise SystemExit("--phase finetune needs --weights (a 3D pre-training checkpoint); to train the segmenter from random weights use --phase scratch")
+    if args.phase == "scratch" and args.weights:
+        raise SystemExit("--phase scratch starts from random weights: drop --weights or use --phase finetune")
+    if args.b < 1 or args.epochs < 1 or args.steps_per_epoch < 0:
+        raise SystemExit("--b and --epochs must be positive, --steps_per_epoch non-negative")
+
+
+def train(args):
+    check_train(args)
+    from .main import launch
+    launch(args)
+    from .train_seg import train_segmenter
+    return train_segmenter(args)
+
+
+def predict(args):
+    from .data_seg import parse_crop
+    parse_crop(args.crop)
+    if args.b < 1:
+        raise SystemExit("--b must be positive")
+    from .train_seg import predict as run
+    return run(args)
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description="3D segmentation fine-tuning of the PCRLv2 network (HIP kernels on MI355X)")
+    sub = ap.add_subparsers(dest="command", required=True)
+    tr = sub.add_parser("train", help="fine-tune (or train from scratch) the segmenter")
+    tr.add_argument("--data", required=True, help="directory of cases (see the module docstring), or 'synthetic'")
+    tr.add_argument("--phase", default="finetune", choices=("finetune", "scratch"))
+    tr.add_argument("--weights", default="", help="3D pre-training checkpoint (--phase finetune)")
+    tr.add_argument("--n_class", type=int, default=3, help="classes = bits of the label byte, 1..7")
+    tr.add_argument("--in_channels", type=int, default=1)
+    tr.add_argument("--crop", default="64,64,32", help="training crop = evaluation patch, x,y,z, multiples of 8")
+    tr.add_argument("--b", type=int, default=8, help="batch size PER PROCESS")
+    tr.add_argument("--epochs", type=int, default=100, help="last epoch index (inclusive)")
+    tr.add_argument("--lr", type=float, default=1e-2)
+    tr.add_argument("--momentum", type=float, default=0.9)
+    tr.add_argument("--weight_decay", type=float, default=1e-4)
+    tr.add_argument("--gpus", default="0", help="visible device ids, comma separated")
+    tr.add_argument("--amp", action="store_true", help="bfloat16 activations and MFMA operands")
+    tr.add_argument("--val_every", type=int, default=0, help="validation after every N-th epoch; 0 = every epoch")
+    tr.add_argument("--save_best", action="store_true", help="write pcrlv2_seg3d_<phase>_1.0_best.pt whenever the mean validation Dice improves")
+    tr.add_argument("--resume", default="", help="checkpoint to continue from (model, momentum buffers, epoch)")
+    tr.add_argument("--output", default="./model_seg3d", help="checkpoint directory")
+    tr.add_argument("--seed", type=int, default=42)
+    tr.add_argument("--steps_per_epoch", type=int, default=0, help="batches per epoch; 0 = one crop per training case")
+    tr.add_argument("--workers", type=int, default=4)
+    tr.set_defaults(model="pcrlv2", n="seg3d", ratio=1.0)
+    pr = sub.add_parser("predict", help="write <case>_pred.npy (uint8 bitmask) for every case of a list")
+    pr.add_argument("--data", required=True, help="directory with <case>_img.npy")
+    pr.add_argument("--list", required=True, help="file of case names (in --data, or a path)")
+    pr.add_argument("--weights", required=True, help="a checkpoint of `train`")
+    pr.add_argument("--out", required=True, help="output directory")
+    pr.add_argument("--crop", default="64,64,32", help="the crop the segmenter was trained on")
+    pr.add_argument("--b", type=int, default=8, help="patches per forward")
+    pr.add_argument("--amp", action="store_true")
+    pr.add_argument("--gpu", type=int, default=0)
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    return {"train": train, "predict": predict}[args.command](args)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

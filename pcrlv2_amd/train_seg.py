@@ -1,0 +1,181 @@
+"""3D segmentation fine-tuning on the MI355X engine: `seg3d.py train | predict` -- the downstream use of the WHOLE pre-trained 3D network, decoder
+included (the reference's README, "Load the Encoder Part of a 3D Model", loads all of PCRLv23d; BraTS and LiTS in the paper).
+
+The reference's fine-tune branch is not public.  What is pinned: the model (models.Segmenter3d IS a PCRLv23d(n_class, in_channels): a fine-tuned
+checkpoint loads into the reference's class) and the optimiser / schedule of its 3D pre-training (SGD, cosine).  This project's own choices: the loss
+wb * BCE + wd * (1 - mean Dice) on overlapping sigmoid regions, mean per-case Dice as the metric, crops and stride-tiled evaluation (data_seg).
+
+The run, the epoch and the bracket around a step are pcrlv2_amd.loop's; validation is ONE pass of Segmenter3d.infer over the tiles with the integer
+counts {TP, |pred|, |gt|} per (case, class) and the loss sums kept on the device, one all_reduce of both when there is a process group (cases are
+sharded by rank, every rank indexes the global case table) and one host read-back.
+"""
+from __future__ import print_function
+
+import os
+import sys
+
+import numpy as np
+import torch
+import torch.distributed as dist
+
+from . import data_seg as _data
+from . import loop as _loop
+from .loop import to_gpu
+from .models import Segmenter3d
+from .optim import FusedSGD
+
+
+def dice_from_counts(counts):
+    """Host, float64: counts [cases][K][3] = {TP, |pred|, |gt|} (nested lists or a tensor) -> (per-class Dice averaged over the cases [K], their mean over
+    the classes).  A (case, class) pair with empty prediction AND empty ground truth scores 1; an empty prediction against a non-empty ground truth
+    scores 0 by the formula.  No cases: NaN."""
+    rows = counts.tolist() if torch.is_tensor(counts) else counts
+    if not rows:
+        return [], float("nan")
+    K = len(rows[0])
+    per = []
+    for k in range(K):
+        ds = [1.0 if (r[k][1] + r[k][2]) == 0 else 2.0 * float(r[k][0]) / float(r[k][1] + r[k][2]) for r in rows]
+        per.append(sum(ds) / len(ds))
+    return per, sum(per) / K
+
+
+def loss_from_sums(sums, K, wb=1.0, wd=1.0):
+    """Host: the operator's loss from its float64 sums [4 K + 1] ({I, P, G, BCE} per class, then the counted voxels), here over a whole pass."""
+    mc = sums[4 * K]
+    bce = sum(sums[4 * k + 3] for k in range(K)) / (mc * K) if mc > 0 else 0.0
+    dice = sum((2.0 * sums[4 * k] + 1.0) / (sums[4 * k + 1] + sums[4 * k + 2] + 1.0) for k in range(K)) / K
+    return wb * bce + wd * (1.0 - dice)
+
+
+def higher_dice(val, best):
+    """--save_best: the mean validation Dice improves strictly; NaN is never best."""
+    m = val["mean_dice"]
+    return m == m and (best is None or m > best["mean_dice"])
+
+
+def train_step(model, optimizer, batch):
+    """One optimisation step on (x [B,C,X,Y,Z] float32, labels uint8 [B,X,Y,Z]).  -> (loss, sums), detached."""
+    def forward():
+        x = to_gpu(batch[0])
+        return model.loss(x, batch[1].to(x.device, non_blocking=True))
+
+    loss, sums = _loop.run_step(model, optimizer, forward, ("3d-seg", tuple(batch[0].shape)))
+    return loss.detach(), sums.detach()
+
+
+def evaluate(model, loader, group=None):
+    """One pass of `model.infer` over the tiles of `loader` (data_seg.TileLoader: this rank's cases).  -> {'loss', 'dice': [K], 'mean_dice', 'cases'}"""
+    dev = next(model.parameters()).device
+    K, n_cases = model.n_class, len(loader.cases)
+    ns = 4 * K + 1
+    counts = torch.zeros((max(n_cases, 1), K, 3), dtype=torch.int64, device=dev)
+    acc = torch.zeros(ns + n_cases * K * 3, dtype=torch.float64, device=dev)       # the loss sums, then the counts (< 2^53: exact in float64)
+
+    def per_batch(batch):
+        x = batch[0].to(dev, non_blocking=True).float()
+        _, _, sums, _ = model.infer(x, labels=batch[1].to(dev), case_index=batch[2].to(dev), counts=counts)
+        acc[:ns] += sums
+
+    def counts_into_acc():       # runs once after the last batch, in front of the all_reduce: ONE collective carries counts and sums
+        acc[ns:] = counts[:n_cases].reshape(-1).double()
+        return acc.new_zeros(0)
+
+    host = _loop.held_out_pass(loader, group, acc, per_batch, also_read=counts_into_acc)
+    table = [[[int(v) for v in host[ns + (c * K + k) * 3:ns + (c * K + k) * 3 + 3]] for k in range(K)] for c in range(n_cases)]
+    per, mean = dice_from_counts(table)
+    return {"loss": loss_from_sums(host[:ns], K, model.wb, model.wd) if n_cases else float("nan"), "dice": per, "mean_dice": mean, "cases": n_cases}
+
+
+def _fmt(val):
+    return 'loss {0:.4f}\tmean Dice {1:.4f}\t({2} cases)'.format(val["loss"], val["mean_dice"], val["cases"])
+
+
+def resume_segmenter(path, model, optimizer, rank):
+    ckpt = torch.load(path, map_location="cpu", weights_only=False)
+    model.load_state_dict(ckpt["state_dict"])
+    if "optimizer" in ckpt:
+        optimizer.load_state_dict(ckpt["optimizer"])
+    return int(ckpt.get("epoch", -1))
+
+
+def train_segmenter(args):
+    """-> the trained model (`.test_metrics`: the final test's)."""
+    return _loop.run_with_group(lambda distributed: _train_segmenter(args, distributed))
+
+
+def _train_segmenter(args, distributed):
+    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+    loaders = _data.loaders(args, rank, world)
+
+    def make(rank):
+        return Segmenter3d(args.n_class, in_channels=args.in_channels, weights=args.weights if args.phase == "finetune" else None)
+
+    task = _loop.Task(
+        make_model=make,
+        make_optimizer=lambda params, **k: FusedSGD([p for p in params if p.requires_grad], **k),      # only what the loss reaches: the heads are frozen
+        resume=resume_segmenter,
+        resumed="==> resumed the segmenter from {}; continuing with epoch {}",
+        state_dict=lambda model: model.state_dict(),
+        epoch=lambda epoch, loader, model, optimizer, verbose: _loop.run_epoch(epoch, loader, model, lambda batch: train_step(model, optimizer, batch),
+                                                                               (("seg loss", 0),), verbose),
+        validate=lambda model, loader, epoch: evaluate(model, loader),
+        val_text=_fmt, better=higher_dice, best_keys=('epoch', 'state_dict', 'val'),
+        val_every_0_is_1=True, save_last=True)
+    model, last_epoch, chatty = _loop.run_epochs(args, loaders, task, distributed)
+    if last_epoch is not None:       # the final test: the best model by validation Dice when one was kept, otherwise the last epoch's
+        if distributed:
+            dist.barrier()
+        best_file = _loop.checkpoint_name(args, "best")
+        which = "last epoch %d" % last_epoch
+        if getattr(args, "save_best", False) and os.path.exists(best_file):
+            ckpt = torch.load(best_file, map_location="cpu", weights_only=False)
+            model.load_state_dict(ckpt["state_dict"])
+            which = "best epoch %d" % ckpt["epoch"]
+        test = evaluate(model, loaders['test'])
+        if chatty:
+            print('Test: ({0})\t{1}\tper class {2}'.format(which, _fmt(test), " ".join("%.4f" % d for d in test["dice"])))
+            sys.stdout.flush()
+        model.test_metrics = test
+    return model
+
+
+# ---- predict ----------------------------------------------------------------------------------------------------------------------
+def load_segmenter(weights, device, amp=False):
+    if not os.path.isfile(weights):
+        raise SystemExit(f"--weights {weights}: no such file (a checkpoint written by `seg3d.py train`)")
+    sd = torch.load(weights, map_location="cpu", weights_only=False)["state_dict"]
+    model = Segmenter3d(sd["out_tr.final_conv.weight"].shape[0], in_channels=sd["down_tr64.ops.0.conv1.weight"].shape[1])
+    model.load_state_dict(sd)
+    model = model.to(device)
+    if amp:
+        model.set_compute_dtype(torch.bfloat16)
+    return model
+
+
+def predict_case(model, case, crop, b):
+    """The predicted bitmask uint8 [X, Y, Z] of one case, stitched from its tiles (each voxel from the one tile that counts it)."""
+    dev = next(model.parameters()).device
+    out = np.zeros(case.shape, dtype=np.uint8)
+    for x, lab, _, starts in _data.TileLoader([case], crop, b):
+        mask = model.infer(to_gpu(x), labels=(lab & _data.NOT_COUNTED).to(dev), want_mask=True)[3].cpu().numpy()
+        for m, l, st in zip(mask, lab.numpy(), starts.tolist()):
+            own = (l & _data.NOT_COUNTED) == 0
+            idx = np.nonzero(own)
+            out[idx[0] + st[0], idx[1] + st[1], idx[2] + st[2]] = m[own]
+    return out
+
+
+def predict(args, log=print):
+    crop = _data.parse_crop(args.crop)
+    device = torch.device("cuda", args.gpu)
+    torch.cuda.set_device(device)
+    model = load_segmenter(args.weights, device, args.amp)
+    os.makedirs(args.out, exist_ok=True)
+    names = _data.read_list(args.data, args.list)
+    for name in names:
+        case = _data.open_case(args.data, name, model.n_class, model.in_channels, need_seg=False)
+        case.seg = None          # the prediction does not look at labels
+        np.save(os.path.join(args.out, name + "_pred.npy"), predict_case(model, case, crop, args.b))
+    log(f"[seg3d] {len(names)} masks written to {args.out}")
+    return len(names)
