@@ -263,6 +263,8 @@ int pcrl_bn1d_fwd(const float* x, float* y, const float* gamma, const float* bet
                   float momentum, float eps, float* mean, float* rstd, int rows, int C, int relu, pcrl_stream_t stream);
 int pcrl_bn1d_bwd(const float* dy, const float* x, const float* y, const float* gamma, const float* mean, const float* rstd,
                   float* dx, float* dgamma, float* dbeta, int rows, int C, int relu, pcrl_stream_t stream);
+/* eval mode, any C: y = scale[c] * x + shift[c] (+ReLU) with the coefficients of the running statistics (C % 4 == 0 also runs on pcrl_bn_act_apply) */
+int pcrl_bn1d_eval(const float* x, float* y, const float* scale, const float* shift, int rows, int C, int relu, pcrl_stream_t stream);
 int pcrl_linear_fwd(const float* x, const float* w, const float* b, float* y, int rows, int Cin, int Cout, pcrl_stream_t stream);
 int pcrl_linear_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, float* db,
                     int rows, int Cin, int Cout, pcrl_stream_t stream);
@@ -280,7 +282,8 @@ int pcrl_sigmoid_bwd(const float* dout, const float* out, float* dpre, int64_t n
 
 /* ---------------------------------------------------------------------------------------
  * Losses -- aten::mse_loss (train_3d.py:56,135,137) and aten::cosine_similarity(dim=1, eps=1e-8).mean()
- * (train_3d.py:57,90-91).  ws: pcrl_reduce_ws_bytes(n). */
+ * (train_3d.py:57,90-91).  ws: pcrl_reduce_ws_bytes(n).  The cosine is x.y / (max(|x|, eps) max(|y|, eps)) with an active clamp
+ * treated as a constant in the backward; ATen applies its clamp under no-grad, so its gradient differs on rows with 0 < |x| <= eps. */
 size_t pcrl_reduce_ws_bytes(int64_t n);
 int pcrl_mse_fwd(const float* p, const float* gt, float* loss, void* ws, size_t ws_bytes, int64_t n, pcrl_stream_t stream);
 int pcrl_mse_bwd(const float* p, const float* gt, const float* dloss, float* dp, int64_t n, pcrl_stream_t stream);

@@ -755,6 +755,23 @@ extern "C" int pcrl_bn1d_bwd(const float* dy, const float* x, const float* y, co
   hipLaunchKernelGGL(bn1d_bwd_kernel, dim3((C + 3) / 4), dim3(256), 0, as_stream(stream), dy, x, y, gamma, mean, rstd, dx, dgamma, dbeta, rows, C, relu);
   return pcrl_check_launch("bn1d_bwd");
 }
+// Eval-mode BatchNorm1d (+ReLU), y = scale[c] * x + shift[c], one element per thread: the channel counts the vectorised apply kernel
+// (pcrl_bn_act_apply: C % 4 == 0) does not take -- the training-mode kernels above take any C, so must the eval forward of the same head.
+static __global__ void __launch_bounds__(256) bn1d_eval_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ scale,
+                                                               const float* __restrict__ shift, int64_t n, int C, int relu) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int c = (int)(i % C);
+    float v = scale[c] * x[i] + shift[c];
+    if (relu && v < 0.f) v = 0.f;
+    y[i] = v;
+  }
+}
+extern "C" int pcrl_bn1d_eval(const float* x, float* y, const float* scale, const float* shift, int rows, int C, int relu, pcrl_stream_t stream) {
+  PCRL_REQUIRE(x && y && scale && shift && rows > 0 && C > 0, "bn1d_eval: bad arguments");
+  const int64_t n = (int64_t)rows * C;
+  hipLaunchKernelGGL(bn1d_eval_kernel, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), x, y, scale, shift, n, C, relu);
+  return pcrl_check_launch("bn1d_eval");
+}
 static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 extern "C" int pcrl_linear_fwd(const float* x, const float* w, const float* b, float* y, int rows, int Cin, int Cout, pcrl_stream_t stream) {
   PCRL_REQUIRE(x && w && y && rows > 0 && Cin > 0 && Cout > 0, "linear_fwd: bad arguments");

@@ -1351,6 +1351,11 @@ def bn1d_eval(x, gamma, beta, running_mean, running_var, relu: bool):
     """Eval-mode BatchNorm1d (+ReLU) on [rows, C] float32: the per-channel apply kernel with coefficients from the running statistics."""
     rows, C = x.shape
     scale, shift = bn_eval_coef(gamma, beta, running_mean, running_var)
+    if C % 4:      # the vectorised apply kernel takes whole 4-float groups of channels; the training-mode kernels of the heads take any C
+        x = x.contiguous()
+        y = torch.empty_like(x)
+        lib().call("pcrl_bn1d_eval", x, y, scale, shift, rows, C, int(relu), stream_handle())
+        return y
     return bn_act_apply(x.contiguous(), scale, shift, rows, C, ACT_RELU if relu else ACT_NONE, torch.float32)
 
 
