@@ -775,6 +775,33 @@ int pcrl_seg_head_eval(const void* a, const float* w, const float* b, const uint
                        uint8_t* mask, double* sums, float* loss, float wb, float wd, void* ws, size_t ws_bytes, int N, int64_t S, int K, int dtype,
                        pcrl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * 3D path, overlap-blended sliding-window inference of the segmenter (csrc/seg_head.hip, csrc/seg_blend.hip).
+ * pcrl_seg_head_logits -- the head's logits and nothing else: z float32 [N * S][K] from a / w / b as above, with the arithmetic of the three kernels
+ *   above (a logit is bit-identical to the one pcrl_seg_head_eval thresholds).  One read of a; no workspace.
+ * pcrl_seg_cut_patches -- the patches of one case, cut on the device: img [C][X][Y][Z] float32 (src_half = 0) or float16 (src_half = 1); starts int32
+ *   [n][3] on the device; out float32 [n][C][cx][cy][cz] (cz a multiple of 4, out 16-byte aligned), 0 outside the volume.  A pure copy, float16 widened exactly.
+ * pcrl_seg_blend -- the per-patch logits of ONE case z float32 [P][cx][cy][cz][K], P = nx * ny * nz patches in x-major order (p = (ix * ny + iy) * nz
+ *   + iz) at the ascending, distinct starts sx [nx], sy [ny], sz [nz] (int32, device) that cover the volume X x Y x Z, blended with the separable
+ *   window wx [cx], wy [cy], wz [cz] (float32, positive).  Per voxel and class, over the covering patches (s <= v < s + crop) in ascending ix, iy, iz:
+ *       w = (wx[i] * wy[j]) * wz[k];  num_k = num_k + w * z_k;  den = den + w        plain float32 in this order, no fused multiply-add
+ *   labels uint8 [X][Y][Z] or NULL (nothing labelled, everything counted): bits as above.  Outputs, each may be NULL:
+ *     mask   uint8 [X][Y][Z]: bit k = (num_k >= 0) -- no division decides a prediction; 0 where bit 7 of the label is set
+ *     probs  float32 [K][X][Y][Z]: 1 / (1 + exp(-num_k / den))
+ *     numden float32 [2 K + 1][X][Y][Z]: num_k per class, then den, then zbar_k = num_k / den per class (tests)
+ *     sums   float64 [4 K + 1] and loss float32 [1] (both or neither): the head's {I, P, G, BCE} per class and Mc from zbar = num / den over the counted
+ *            voxels, the loss of the head's formula; per-block float64 partials and the head's fixed-order second launch.  ws: pcrl_seg_blend_ws_bytes.
+ *     counts int64 [K][3] (with sums only): {TP, |pred|, |gt|} ADDED to this one row of a counts table with 64-bit integer atomics.
+ *   No floating-point atomics: two runs give identical bytes.
+ *   PCRL_EINVAL for K outside 1..7, an empty volume or crop, and P != nx * ny * nz. */
+int pcrl_seg_head_logits(const void* a, const float* w, const float* b, float* z, int N, int64_t S, int K, int dtype, pcrl_stream_t stream);
+int pcrl_seg_cut_patches(const void* img, int src_half, const int* starts, float* out, int n, int C, int X, int Y, int Z, int cx, int cy, int cz,
+                         pcrl_stream_t stream);
+size_t pcrl_seg_blend_ws_bytes(int X, int Y, int Z);
+int pcrl_seg_blend(const float* z, int64_t P, const int* sx, const int* sy, const int* sz, int nx, int ny, int nz, const float* wx, const float* wy,
+                   const float* wz, int cx, int cy, int cz, int X, int Y, int Z, int K, const uint8_t* labels, uint8_t* mask, float* probs, float* numden,
+                   int64_t* counts, double* sums, float* loss, float wb, float wd, void* ws, size_t ws_bytes, pcrl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

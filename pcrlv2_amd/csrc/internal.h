@@ -120,3 +120,8 @@ int pcrl_upc_wgrad3_launch(const void* dy0, const void* x, float* dweff, void* w
 // ---- norm_pool.hip: weighted column sum, the whole weight gradient of a 1x1x1 convolution to one channel -----------------------------
 size_t pcrl_weighted_colsum_ws_bytes(int64_t M, int C);
 int pcrl_weighted_colsum(const void* v, const float* rowscale, float* out, void* ws, size_t ws_bytes, int64_t M, int C, int dtype, hipStream_t stream);
+
+// ---- seg_head.hip: the fixed-order second launch of the segmentation sums, shared with seg_blend.hip ------------------------------------
+// partial [nb][32] float64 per-block sums (slot k * 4 + {I, P, G, BCE}, slot 28: counted voxels) -> sums [4 K + 1] and loss [1], added in block order
+constexpr int PCRL_SEG_SLOTS = 32, PCRL_SEG_CNT_SLOT = 28;
+void pcrl_seg_sums_launch(const double* partial, int nb, int K, float wb, float wd, double* sums, float* loss, hipStream_t stream);

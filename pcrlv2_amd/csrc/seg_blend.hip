@@ -1,0 +1,250 @@
+// Overlap-blended sliding-window inference of the 3D segmenter: the patches of one case are cut on the device (seg_cut_patches), the network turns
+// each into logits (seg_head.hip's logits kernel), and seg_blend folds the per-patch logits into the case's prediction.  Compiled with
+// -ffp-contract=off: the blend is pinned bit for bit against a float32 restatement that multiplies and adds one operation at a time.
+//
+// blend     one thread per VOLUME voxel, all K classes; consecutive threads move along Z, so the rows of K floats a wave reads from one patch are
+//           consecutive (a contiguous run of 64 K floats where the wave stays inside one patch row), and the mask store is one byte per thread, 64
+//           consecutive bytes per wave.  Per axis the covering patches s <= v < s + crop are a contiguous range of the ascending start list, found once
+//           per voxel by two binary searches; the voxel then visits ix, iy, iz in ascending order:
+//               w = (wx[i] * wy[j]) * wz[k];   num_k = num_k + w * z_k;   den = den + w            plain float32, this order, no fused multiply-add
+//           pred_k = (num_k >= 0): den > 0, so no division decides a prediction.  zbar = num / den feeds the probabilities and, with `sums`, the head's
+//           per-voxel terms (I, P, G, BCE: seg_head.hip's expressions) in per-thread float64 sums and the integer counts {TP, |pred|, |gt|}.
+//           Every read of z is guarded by its own coverage test, so a start list that breaks the contract (not ascending) cannot index outside z.
+// sums      wave shuffle sums, then LDS red[wave][slot] (float64) and redc[wave][k * 3 + q] (integers), as seg_head.hip: per-block float64 partials
+//           that seg_head.hip's one-block launch adds in block order (pcrl_seg_sums_launch), and ONE 64-bit integer atomic per (block, k, q) into the
+//           case's row of counts.  No floating-point atomics: two runs give identical bytes.
+// LDS       only this combination at the end of a block.  After the shuffle sums every lane holds the wave's totals; lane 0 of each wave alone writes
+//           them, one scalar store per slot -- a store instruction with ONE active lane has no second address to conflict with.  The readers are
+//           threads t < 29 (t < 3 K) at consecutive float64 (uint32) words of one wave's row, the four rows in turn: consecutive banks, each hit
+//           once per instruction -- conflict-free.  There is no LDS traffic inside the voxel loop.
+// cut       a pure copy: thread = 4 consecutive z of one (patch, channel, x, y) row; four scalar loads (the source run starts at any z), one 16-byte
+//           store; what lies outside the volume is 0, and float16 sources are widened exactly.
+#include "internal.h"
+
+namespace {
+
+constexpr int SB_THREADS = 256, SB_MAX_K = 7, SB_MAX_BLOCKS = 1024;
+
+struct SbGeom {
+  int X, Y, Z, cx, cy, cz, nx, ny, nz;
+};
+
+__device__ __forceinline__ float sb_sigmoid(float z) { return 1.0f / (1.0f + expf(-z)); }      // sh_sigmoid's expression
+
+// first index i of the ascending list s[0..n) with s[i] > t (n: none)
+__device__ __forceinline__ int sb_first_above(const int* __restrict__ s, int n, int t) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (s[mid] > t) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ unsigned sb_wave_sum(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
+  return v;
+}
+
+inline int sb_blocks(int64_t V) {
+  const int64_t want = (V + SB_THREADS - 1) / SB_THREADS;
+  return (int)(want < SB_MAX_BLOCKS ? want : SB_MAX_BLOCKS);
+}
+
+// grid = sb_blocks(V); block = 256.  partial[block][32] float64 (seg_head.hip's slots) with STATS.
+template <int K, bool STATS>
+__global__ void __launch_bounds__(SB_THREADS) seg_blend_kernel(const float* __restrict__ z, const int* __restrict__ sx, const int* __restrict__ sy,
+                                                              const int* __restrict__ sz, const float* __restrict__ wx, const float* __restrict__ wy,
+                                                              const float* __restrict__ wz, SbGeom g, const uint8_t* __restrict__ labels,
+                                                              uint8_t* __restrict__ mask, float* __restrict__ probs, float* __restrict__ numden,
+                                                              unsigned long long* __restrict__ counts, double* __restrict__ partial) {
+  __shared__ double red[SB_THREADS / 64][PCRL_SEG_SLOTS];
+  __shared__ unsigned redc[SB_THREADS / 64][SB_MAX_K * 3 + 3];
+  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+  const int64_t V = (int64_t)g.X * g.Y * g.Z;
+  double sI[K], sP[K], sG[K], sB[K];
+  unsigned cTP[K], cPr[K], cGt[K], cnt = 0;
+#pragma unroll
+  for (int c = 0; c < K; ++c) {
+    sI[c] = sP[c] = sG[c] = sB[c] = 0.0;
+    cTP[c] = cPr[c] = cGt[c] = 0u;
+  }
+  for (int64_t v = (int64_t)blockIdx.x * SB_THREADS + t; v < V; v += (int64_t)gridDim.x * SB_THREADS) {
+    const int zc = (int)(v % g.Z), yc = (int)((v / g.Z) % g.Y), xc = (int)(v / ((int64_t)g.Z * g.Y));
+    const int x0 = sb_first_above(sx, g.nx, xc - g.cx), x1 = sb_first_above(sx, g.nx, xc);
+    const int y0 = sb_first_above(sy, g.ny, yc - g.cy), y1 = sb_first_above(sy, g.ny, yc);
+    const int z0 = sb_first_above(sz, g.nz, zc - g.cz), z1 = sb_first_above(sz, g.nz, zc);
+    float num[K], den = 0.0f;
+#pragma unroll
+    for (int c = 0; c < K; ++c) num[c] = 0.0f;
+    for (int ix = x0; ix < x1; ++ix) {
+      const int i = xc - sx[ix];
+      if ((unsigned)i >= (unsigned)g.cx) continue;
+      const float wi = wx[i];
+      for (int iy = y0; iy < y1; ++iy) {
+        const int j = yc - sy[iy];
+        if ((unsigned)j >= (unsigned)g.cy) continue;
+        const float wij = wi * wy[j];
+        const int64_t prow = ((((int64_t)ix * g.ny + iy) * g.nz) * g.cx + i) * g.cy + j;       // (patch (ix, iy, 0), i, j) in rows of cz voxels
+        for (int iz = z0; iz < z1; ++iz) {
+          const int k = zc - sz[iz];
+          if ((unsigned)k >= (unsigned)g.cz) continue;
+          const float w = wij * wz[k];
+          const float* __restrict__ row = z + ((prow + (int64_t)iz * g.cx * g.cy) * g.cz + k) * K;
+#pragma unroll
+          for (int c = 0; c < K; ++c) num[c] = num[c] + w * row[c];
+          den = den + w;
+        }
+      }
+    }
+    const unsigned lab = labels ? labels[v] : 0u;
+    const bool counted = !(lab & 0x80u);
+    unsigned m = 0;
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+      const bool pred = counted && num[c] >= 0.0f;
+      m |= pred ? (1u << c) : 0u;
+      if (numden) {
+        numden[(int64_t)c * V + v] = num[c];
+        numden[(int64_t)(K + 1 + c) * V + v] = num[c] / den;
+      }
+      if (probs || STATS) {
+        const float zb = num[c] / den, p = sb_sigmoid(zb);
+        if (probs) probs[(int64_t)c * V + v] = p;
+        if (STATS && counted) {
+          const bool gt = (lab >> c) & 1u;
+          const float y = gt ? 1.0f : 0.0f;
+          sI[c] += (double)(gt ? p : 0.0f);
+          sP[c] += (double)p;
+          sG[c] += (double)y;
+          sB[c] += (double)(fmaxf(zb, 0.0f) - y * zb + log1pf(expf(-fabsf(zb))));
+          cTP[c] += (pred && gt) ? 1u : 0u;
+          cPr[c] += pred ? 1u : 0u;
+          cGt[c] += gt ? 1u : 0u;
+        }
+      }
+    }
+    if (numden) numden[(int64_t)K * V + v] = den;
+    if (mask) mask[v] = (uint8_t)m;
+    cnt += counted ? 1u : 0u;
+  }
+  if (!STATS) return;
+#pragma unroll
+  for (int c = 0; c < K; ++c) {
+    const double a = wave_sum(sI[c]), b = wave_sum(sP[c]), d = wave_sum(sG[c]), e = wave_sum(sB[c]);
+    const unsigned p = sb_wave_sum(cTP[c]), q = sb_wave_sum(cPr[c]), r = sb_wave_sum(cGt[c]);
+    if (lane == 0) {
+      red[wid][c * 4 + 0] = a;
+      red[wid][c * 4 + 1] = b;
+      red[wid][c * 4 + 2] = d;
+      red[wid][c * 4 + 3] = e;
+      redc[wid][c * 3 + 0] = p;
+      redc[wid][c * 3 + 1] = q;
+      redc[wid][c * 3 + 2] = r;
+    }
+  }
+  cnt = sb_wave_sum(cnt);
+  if (lane == 0) red[wid][PCRL_SEG_CNT_SLOT] = (double)cnt;
+  __syncthreads();
+  if (t < 4 * K || t == PCRL_SEG_CNT_SLOT) partial[(int64_t)blockIdx.x * PCRL_SEG_SLOTS + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+  if (counts && t < 3 * K) atomicAdd(&counts[t], (unsigned long long)redc[0][t] + redc[1][t] + redc[2][t] + redc[3][t]);
+}
+
+template <int K>
+void seg_blend_launch(bool stats, int nb, hipStream_t st, const float* z, const int* sx, const int* sy, const int* sz, const float* wx, const float* wy,
+                      const float* wz, const SbGeom& g, const uint8_t* labels, uint8_t* mask, float* probs, float* numden, int64_t* counts, double* partial) {
+  if (stats)
+    hipLaunchKernelGGL((seg_blend_kernel<K, true>), dim3(nb), dim3(SB_THREADS), 0, st, z, sx, sy, sz, wx, wy, wz, g, labels, mask, probs, numden,
+                       reinterpret_cast<unsigned long long*>(counts), partial);
+  else
+    hipLaunchKernelGGL((seg_blend_kernel<K, false>), dim3(nb), dim3(SB_THREADS), 0, st, z, sx, sy, sz, wx, wy, wz, g, labels, mask, probs, numden, nullptr,
+                       nullptr);
+}
+
+// grid = ceil(total / 256) with total = n * C * cx * cy * (cz / 4); block = 256.
+template <typename T>
+__global__ void __launch_bounds__(SB_THREADS) seg_cut_kernel(const T* __restrict__ img, const int* __restrict__ starts, float* __restrict__ out, int64_t total,
+                                                            int C, int X, int Y, int Z, int cx, int cy, int cz) {
+  const int64_t q = (int64_t)blockIdx.x * SB_THREADS + threadIdx.x;
+  if (q >= total) return;
+  const int cz4 = cz >> 2;
+  const int k4 = (int)(q % cz4);
+  int64_t r = q / cz4;
+  const int j = (int)(r % cy);
+  r /= cy;
+  const int i = (int)(r % cx);
+  r /= cx;
+  const int c = (int)(r % C);
+  const int64_t p = r / C;
+  const int64_t x = (int64_t)starts[p * 3] + i, y = (int64_t)starts[p * 3 + 1] + j, z0 = (int64_t)starts[p * 3 + 2] + 4 * k4;
+  const bool row_in = x >= 0 && x < X && y >= 0 && y < Y;
+  const T* __restrict__ src = img + (((int64_t)c * X + (row_in ? x : 0)) * Y + (row_in ? y : 0)) * Z;
+  float4 o;
+  float* ov = reinterpret_cast<float*>(&o);
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int64_t zz = z0 + u;
+    ov[u] = (row_in && zz >= 0 && zz < Z) ? (float)src[zz] : 0.0f;
+  }
+  *reinterpret_cast<float4*>(out + q * 4) = o;
+}
+
+}  // namespace
+
+extern "C" size_t pcrl_seg_blend_ws_bytes(int X, int Y, int Z) {
+  if (X <= 0 || Y <= 0 || Z <= 0) return 0;
+  return (size_t)sb_blocks((int64_t)X * Y * Z) * PCRL_SEG_SLOTS * sizeof(double);
+}
+
+extern "C" int pcrl_seg_blend(const float* z, int64_t P, const int* sx, const int* sy, const int* sz, int nx, int ny, int nz, const float* wx,
+                              const float* wy, const float* wz, int cx, int cy, int cz, int X, int Y, int Z, int K, const uint8_t* labels, uint8_t* mask,
+                              float* probs, float* numden, int64_t* counts, double* sums, float* loss, float wb, float wd, void* ws, size_t ws_bytes,
+                              pcrl_stream_t stream) {
+  PCRL_REQUIRE(K >= 1 && K <= SB_MAX_K, "seg_blend: 1 <= K <= %d classes (bit 7 of a label byte means 'not counted'), got %d", SB_MAX_K, K);
+  PCRL_REQUIRE(X > 0 && Y > 0 && Z > 0, "seg_blend: empty volume %d x %d x %d", X, Y, Z);
+  PCRL_REQUIRE(cx > 0 && cy > 0 && cz > 0, "seg_blend: bad crop %d x %d x %d", cx, cy, cz);
+  PCRL_REQUIRE(nx > 0 && ny > 0 && nz > 0 && (int64_t)nx * ny * nz == P, "seg_blend: %lld patches against start lists of %d x %d x %d", (long long)P, nx,
+               ny, nz);
+  PCRL_REQUIRE(z && sx && sy && sz && wx && wy && wz, "seg_blend: null pointer");
+  PCRL_REQUIRE((sums != nullptr) == (loss != nullptr), "seg_blend: sums and loss are both given or both NULL");
+  PCRL_REQUIRE(!counts || sums, "seg_blend: counts are produced with the sums");
+  const bool stats = sums != nullptr;
+  if (stats && (!ws || ws_bytes < pcrl_seg_blend_ws_bytes(X, Y, Z))) return pcrl_fail(PCRL_EWORKSPACE, "seg_blend: workspace too small");
+  const SbGeom g{X, Y, Z, cx, cy, cz, nx, ny, nz};
+  const int nb = sb_blocks((int64_t)X * Y * Z);
+  double* partial = static_cast<double*>(ws);
+  hipStream_t st = as_stream(stream);
+#define SB_BLEND(KK) seg_blend_launch<KK>(stats, nb, st, z, sx, sy, sz, wx, wy, wz, g, labels, mask, probs, numden, counts, partial)
+  switch (K) {
+    case 1: SB_BLEND(1); break;
+    case 2: SB_BLEND(2); break;
+    case 3: SB_BLEND(3); break;
+    case 4: SB_BLEND(4); break;
+    case 5: SB_BLEND(5); break;
+    case 6: SB_BLEND(6); break;
+    default: SB_BLEND(7); break;
+  }
+#undef SB_BLEND
+  if (stats) pcrl_seg_sums_launch(partial, nb, K, wb, wd, sums, loss, st);
+  return pcrl_check_launch("seg_blend");
+}
+
+extern "C" int pcrl_seg_cut_patches(const void* img, int src_half, const int* starts, float* out, int n, int C, int X, int Y, int Z, int cx, int cy, int cz,
+                                    pcrl_stream_t stream) {
+  PCRL_REQUIRE(img && starts && out, "seg_cut_patches: null pointer");
+  PCRL_REQUIRE(reinterpret_cast<uintptr_t>(out) % 16 == 0, "seg_cut_patches: out must be 16-byte aligned (16-byte stores)");
+  PCRL_REQUIRE(n > 0 && C > 0 && X > 0 && Y > 0 && Z > 0, "seg_cut_patches: bad sizes n=%d C=%d volume %d x %d x %d", n, C, X, Y, Z);
+  PCRL_REQUIRE(cx > 0 && cy > 0 && cz > 0 && cz % 4 == 0, "seg_cut_patches: bad crop %d x %d x %d (cz is a multiple of 4)", cx, cy, cz);
+  const int64_t total = (int64_t)n * C * cx * cy * (cz / 4), blocks = (total + SB_THREADS - 1) / SB_THREADS;
+  PCRL_REQUIRE(blocks < ((int64_t)1 << 31), "seg_cut_patches: too many output voxels in one call");
+  hipStream_t st = as_stream(stream);
+  if (src_half)
+    hipLaunchKernelGGL(seg_cut_kernel<_Float16>, dim3((unsigned)blocks), dim3(SB_THREADS), 0, st, static_cast<const _Float16*>(img), starts, out, total, C, X, Y,
+                       Z, cx, cy, cz);
+  else
+    hipLaunchKernelGGL(seg_cut_kernel<float>, dim3((unsigned)blocks), dim3(SB_THREADS), 0, st, static_cast<const float*>(img), starts, out, total, C, X, Y, Z, cx,
+                       cy, cz);
+  return pcrl_check_launch("seg_cut_patches");
+}

@@ -14,17 +14,21 @@
 //           per block and left as per-block partials that a second launch adds in block order.  No floating-point atomics anywhere.
 // eval      the forward plus exact integer counts of TP, |pred|, |gt| per (case, class) with pred = (z >= 0) (= p >= 0.5 without a rounded sigmoid);
 //           block sums enter counts[case][k][3] with 64-bit integer atomics (order-independent, as auroc.hip), and optionally the predicted bitmask.
+// logits    the same read of a and the same sh_logit, nothing else: lane sub < K of a voxel stores z_k as float32 at z[voxel][sub].  The voxels of a
+//           wave are consecutive, so a store instruction writes one contiguous run of (64 / LPV) * K floats.  No LDS, no sums, no workspace.  This is
+//           what overlap-blended sliding windows (seg_blend.hip) average; a logit is bit-identical to the one the eval kernel thresholds.
 // The weight lives in registers: lane `sub` holds W[k][sub * V .. sub * V + V) for every k (K * V floats), read once per block from global memory.
 // LDS is used only for the block-level combination at the end of a block: red[wave][slot] (float64), redc[wave][k * 3 + q] (integers) and
 // redw[wave][k * 64 + c] (float32).  Writers are the first LPV lanes of each wave: one scalar store per (k, j), lane `sub` at word k * 64 + sub * V + j,
 // so the LPV <= 16 lanes of a store are V words apart -- at most 16 distinct banks of the 64, each hit once: conflict-free; readers are consecutive
 // threads at consecutive words of one wave's row, four rows in turn (conflict-free).  There is no LDS traffic inside the voxel loop.
-#include "common.h"
+#include "internal.h"
 
 namespace {
 
 constexpr int SH_THREADS = 256, SH_C = 64, SH_MAX_K = 7, SH_MAX_BLOCKS = 1024, SH_SLOTS = 32, SH_CNT = 28, SH_SLICES = 8;
 constexpr float SH_EPS = 1.0f;
+static_assert(SH_SLOTS == PCRL_SEG_SLOTS && SH_CNT == PCRL_SEG_CNT_SLOT, "seg_blend.hip writes its partials in this layout");
 
 __host__ __device__ inline int sh_wstride(int K) { return K * (SH_C + 1); }   // floats of one block's dW [K][64] + db [K] partial
 
@@ -317,6 +321,31 @@ __global__ void __launch_bounds__(SH_THREADS) seg_head_wsum_kernel(const float* 
   }
 }
 
+// grid = (gx, N); block = 256.  z float32 [N * S][K]: the logits, and nothing else.
+template <typename T, int K>
+__global__ void __launch_bounds__(SH_THREADS) seg_head_logits_kernel(const T* __restrict__ a, const float* __restrict__ W, const float* __restrict__ bias,
+                                                                    float* __restrict__ z, int S) {
+  constexpr int V = Vec16<T>::N, LPV = 64 / V, GPB = SH_THREADS / LPV;
+  const int t = threadIdx.x, sub = t % LPV, grp = t / LPV;
+  const int64_t base = (int64_t)blockIdx.y * S;
+  float w[K][V];
+  sh_load_w<T, K>(W, sub, w);
+  const float bk = sub < K ? bias[sub] : 0.0f;
+  const int iters = (S + GPB - 1) / GPB, step = gridDim.x;
+  Vec16<T> x;
+  unsigned lab;
+  int it = blockIdx.x;
+  sh_fetch<T>(a, nullptr, base, it < iters ? it * GPB + grp : S, S, sub, x, lab);
+  for (; it < iters; it += step) {
+    Vec16<T> xn;
+    sh_fetch<T>(a, nullptr, base, it + step < iters ? (it + step) * GPB + grp : S, S, sub, xn, lab);
+    const float zk = sh_logit<T, K>(x, w, bk, sub);
+    const int s = it * GPB + grp;
+    if (sub < K && s < S) z[(base + s) * K + sub] = zk;
+    x = xn;
+  }
+}
+
 int seg_head_check(const char* what, int N, int64_t S, int K, int dtype) {
   PCRL_REQUIRE(N > 0 && S > 0 && S < ((int64_t)1 << 31) - 4096, "%s: bad sizes N=%d S=%lld", what, N, (long long)S);
   PCRL_REQUIRE(N <= 65535, "%s: at most 65535 samples per call, got %d", what, N);
@@ -369,11 +398,33 @@ int seg_head_forward(const char* what, bool eval, const void* a, const float* w,
   else seg_head_launch_fwd<float, KK>(eval, grid, st, a, w, b, labels, partial, case_index, counts, n_cases, mask, (int)S)
   SH_DISPATCH_K(SH_FWD)
 #undef SH_FWD
-  hipLaunchKernelGGL(seg_head_sums_kernel, dim3(1), dim3(SH_THREADS), 0, st, partial, gx * N, K, wb, wd, sums, loss);
+  pcrl_seg_sums_launch(partial, gx * N, K, wb, wd, sums, loss, st);
   return pcrl_check_launch(what);
 }
 
+template <typename T, int K>
+void seg_head_launch_logits(dim3 grid, hipStream_t st, const void* a, const float* w, const float* b, float* z, int S) {
+  hipLaunchKernelGGL((seg_head_logits_kernel<T, K>), grid, dim3(SH_THREADS), 0, st, static_cast<const T*>(a), w, b, z, S);
+}
+
 }  // namespace
+
+void pcrl_seg_sums_launch(const double* partial, int nb, int K, float wb, float wd, double* sums, float* loss, hipStream_t stream) {
+  hipLaunchKernelGGL(seg_head_sums_kernel, dim3(1), dim3(SH_THREADS), 0, stream, partial, nb, K, wb, wd, sums, loss);
+}
+
+extern "C" int pcrl_seg_head_logits(const void* a, const float* w, const float* b, float* z, int N, int64_t S, int K, int dtype, pcrl_stream_t stream) {
+  if (int rc = seg_head_check("seg_head_logits", N, S, K, dtype)) return rc;
+  PCRL_REQUIRE(a && w && b && z, "seg_head_logits: null pointer");
+  const dim3 grid(sh_gx(N, S), N);
+  hipStream_t st = as_stream(stream);
+#define SH_LOGITS(KK)                                                                                  \
+  if (dtype == PCRL_BF16) seg_head_launch_logits<bf16, KK>(grid, st, a, w, b, z, (int)S);             \
+  else seg_head_launch_logits<float, KK>(grid, st, a, w, b, z, (int)S)
+  SH_DISPATCH_K(SH_LOGITS)
+#undef SH_LOGITS
+  return pcrl_check_launch("seg_head_logits");
+}
 
 extern "C" size_t pcrl_seg_head_ws_bytes(int N, int64_t S, int K) {
   if (N <= 0 || S <= 0 || K < 1 || K > SH_MAX_K) return 0;

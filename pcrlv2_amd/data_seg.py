@@ -8,7 +8,11 @@ Training crops (CropLoader): `crop`-sized, cut on the host; every other crop of 
 placed uniformly; an independent flip per axis is applied identically to image and mask; a volume shorter than the crop on an axis is padded with image
 0 and label 0x80.  Evaluation tiles (TileLoader): every case is covered by crop-sized patches at stride = crop, the last patch of an axis shifted back
 inside the volume; voxels an earlier patch already covered carry bit 7 in the later one, so every voxel of every case is counted exactly once and every
-forward has the training crop's shape.  No overlap blending, no whole-volume forward.
+forward has the training crop's shape.  No whole-volume forward.
+
+Overlap-blended sliding windows (window_axis, windows, blend_weights; the pass itself is train_seg.sliding_window): crop-sized patches at stride
+int(crop * (1 - overlap)), the last one of an axis shifted back inside the volume, every voxel's logits the window-weighted mean over the patches
+that cover it.  The tiled path above is what `--overlap 0` (the default) runs.
 """
 from __future__ import annotations
 
@@ -114,6 +118,66 @@ def tiles(shape, crop):
     """-> [(start (x, y, z), own_from (x, y, z))] in x-major order; a tile counts the voxels at or above own_from on every axis."""
     ax = [tile_axis(s, c) for s, c in zip(shape, crop)]
     return [((a[0], b[0], c[0]), (a[1], b[1], c[1])) for a in ax[0] for b in ax[1] for c in ax[2]]
+
+
+# ---- overlap-blended sliding windows ----------------------------------------------------------------------------------------------
+MAX_OVERLAP = 0.75
+WINDOWS = ("gaussian", "constant")
+
+
+def check_overlap(overlap, flag="--overlap"):
+    try:
+        f = float(overlap)
+    except (TypeError, ValueError):
+        f = float("nan")
+    if not 0.0 <= f <= MAX_OVERLAP:
+        raise SystemExit(f"{flag} {overlap}: a fraction of the crop in [0, {MAX_OVERLAP}] (0: stride-tiled patches, no blending; 0.5: MONAI's and nnU-Net's usual "
+                         "choice; above 0.75 the patch count explodes)")
+    return f
+
+
+def check_window(window, flag="--window"):
+    if window not in WINDOWS:
+        raise SystemExit(f"{flag} {window}: one of {', '.join(WINDOWS)}")
+    return window
+
+
+def window_axis(size, crop, overlap):
+    """The ascending, distinct patch starts along one axis: stride max(1, int(crop * (1 - overlap))), the last patch shifted back inside the volume; a
+    volume no longer than the crop has the one patch at 0 (zero-padded at the high end, as cut pads)."""
+    overlap = check_overlap(overlap)
+    size, crop = int(size), int(crop)
+    if size <= crop:
+        return [0]
+    interval = max(1, int(crop * (1 - overlap)))
+    n = -(-(size - crop) // interval) + 1
+    return sorted({min(i * interval, size - crop) for i in range(n)})
+
+
+def windows(shape, crop, overlap):
+    """-> the three per-axis start lists; the patches run in x-major order: patch (ix * ny + iy) * nz + iz starts at (sx[ix], sy[iy], sz[iz])."""
+    return [window_axis(s, c, overlap) for s, c in zip(shape, crop)]
+
+
+def window_starts(axes):
+    """The start (x, y, z) of every patch of `windows`' lists, in patch order."""
+    return [(a, b, c) for a in axes[0] for b in axes[1] for c in axes[2]]
+
+
+def blend_weights(crop, window):
+    """The separable importance map: three float32 tables wx [cx], wy [cy], wz [cz]; a patch voxel (i, j, k) weighs (wx[i] * wy[j]) * wz[k].  'constant':
+    ones.  'gaussian': exp(-0.5 ((i - (c - 1) / 2) / (0.125 c))^2) (nnU-Net's sigma of an eighth of the crop), float64 rounded once to float32; every
+    entry is positive (at least exp(-8)), so a covered voxel never has weight 0."""
+    check_window(window)
+    out = []
+    for c in crop:
+        c = int(c)
+        if window == "constant":
+            out.append(np.ones(c, dtype=np.float32))
+        else:
+            i = np.arange(c, dtype=np.float64)
+            out.append(np.exp(-0.5 * ((i - (c - 1) / 2.0) / (0.125 * c)) ** 2).astype(np.float32))
+    return out
 
 
 def cut_tile(case, start, own_from, crop):

@@ -529,7 +529,7 @@ class Segmenter3d(PCRLv23d):
     (functions.UpConvsFn), then the output head and the Dice/BCE loss as one operator (functions.SegHeadFn, csrc/seg_head.hip).  The projection,
     predictor and deep-supervision heads are NOT run: their parameters have requires_grad = False here and their running statistics and counters do
     not move; `trainable_parameters()` is what the optimiser gets.  infer(x, ...) is the eval-mode forward on the inference kernels followed by
-    pcrl_seg_head_eval.  labels: uint8 [N, D, H, W], bit k = class k (classes may overlap), bit 7 = the voxel is not counted."""
+    pcrl_seg_head_eval, infer_logits(x) the same forward followed by pcrl_seg_head_logits.  labels: uint8 [N, D, H, W], bit k = class k (classes may overlap), bit 7 = the voxel is not counted."""
 
     _HEADS = ("bn.", "predictor_head.", "deep_supervision_head.")
 
@@ -622,11 +622,25 @@ class Segmenter3d(PCRLv23d):
         -> (counts, loss 0-d, sums float64 [4 K + 1], predicted bitmask uint8 [N, D, H, W] | None)"""
         self._check(x, labels)
         dt = self.compute_dtype
+        fc = self.out_tr.final_conv
+        return ops.seg_head_eval(self._infer_features(x, dt), fc.weight, fc.bias, dt, labels=None if labels is None else labels.contiguous(),
+                                 case_index=case_index, counts=counts, want_mask=want_mask, wb=self.wb, wd=self.wd)
+
+    def _infer_features(self, x, dt):
+        """The last decoder stage's activation of the eval-mode forward on the inference kernels, NDHWC memory in `dt`."""
         h = _eval_encoder(self, x, dt, True, stash=False)
         for name, _, _ in _DECODER:
             up = getattr(self, name)
             h = ops.convt_forward(ops.to_act(h, dt), up.up_conv.weight, up.up_conv.bias, up._packed_up, dt)
             h = _eval_luconv(up.ops[1], _eval_luconv(up.ops[0], h, dt, True), dt, True)
+        return ops.to_act(h, dt)
+
+    @torch.no_grad()
+    def infer_logits(self, x, out=None):
+        """infer's forward followed by the head's logits alone (pcrl_seg_head_logits), whatever `self.training` says; nothing of the model is touched.
+        -> float32 [N, D, H, W, K] (written into `out` when given): thresholding it at 0 is infer's mask, bit for bit.  What overlap-blended
+        sliding windows average (train_seg.sliding_window)."""
+        self._check(x, None)
+        dt = self.compute_dtype
         fc = self.out_tr.final_conv
-        return ops.seg_head_eval(ops.to_act(h, dt), fc.weight, fc.bias, dt, labels=None if labels is None else labels.contiguous(),
-                                 case_index=case_index, counts=counts, want_mask=want_mask, wb=self.wb, wd=self.wd)
+        return ops.seg_head_logits(self._infer_features(x, dt), fc.weight, fc.bias, dt, out=out)

@@ -1706,3 +1706,87 @@ def seg_head_eval(a, w, b, dtype, labels=None, case_index=None, counts=None, wan
     lib().call("pcrl_seg_head_eval", a, wc, bc, labels, case_index, counts, counts.shape[0], mask, sums, loss, wb, wd, ws, nb, N, S, K, dtype_code(dtype),
                stream_handle())
     return counts, loss.view(()), sums, mask
+
+
+# ----------------------------------------------------------------------------------------------
+# overlap-blended sliding-window inference: the head's logits, device-side patch cutting, the blend (csrc/seg_head.hip, csrc/seg_blend.hip)
+# ----------------------------------------------------------------------------------------------
+def seg_head_logits(a, w, b, dtype, out=None):
+    """The head's logits and nothing else (pcrl_seg_head_logits): z float32 [N, D, H, W, K], each bit-identical to the logit seg_head_eval thresholds.
+    `out`: a contiguous float32 tensor of N * D * H * W * K elements on a's device that receives them (a slice of a per-case buffer)."""
+    N, S, K, wc, bc = _seg_args(a, w, b, None, dtype, "seg_head_logits")
+    _, D, H, W, _ = dims(a)
+    if out is None:
+        out = torch.empty((N, D, H, W, K), dtype=torch.float32, device=a.device)
+    elif out.dtype != torch.float32 or out.numel() != N * S * K or not out.is_contiguous() or out.device != a.device:
+        raise PcrlError(f"seg_head_logits: out must be a contiguous float32 tensor of {N * S * K} elements on {a.device}, got {out.dtype} {tuple(out.shape)}")
+    lib().call("pcrl_seg_head_logits", a, wc, bc, out, N, S, K, dtype_code(dtype), stream_handle())
+    return out.view(N, D, H, W, K)
+
+
+def seg_cut_patches(img, starts, crop, out=None):
+    """The crop-sized patches of one case, cut on the device (pcrl_seg_cut_patches): img [C, X, Y, Z] float32 / float16, starts int32 [n, 3] on the same
+    device.  -> float32 [n, C, *crop], 0 outside the volume: data_seg.cut's image, byte for byte."""
+    if img.dim() != 4 or img.dtype not in (torch.float32, torch.float16) or not img.is_contiguous() or not img.is_cuda or img.numel() == 0:
+        raise PcrlError(f"seg_cut_patches: the image must be a contiguous float32 / float16 [C, X, Y, Z] tensor on the GPU, got {img.dtype} {tuple(img.shape)} on {img.device}")
+    if starts.dtype != torch.int32 or starts.dim() != 2 or starts.shape[1] != 3 or starts.shape[0] < 1 or not starts.is_contiguous() or starts.device != img.device:
+        raise PcrlError(f"seg_cut_patches: starts must be a contiguous int32 [n, 3] tensor on {img.device}, got {starts.dtype} {tuple(starts.shape)}")
+    crop = tuple(int(c) for c in crop)
+    if len(crop) != 3 or any(c <= 0 for c in crop) or crop[2] % 4:
+        raise PcrlError(f"seg_cut_patches: crop {crop}: three positive sizes, the last a multiple of 4")
+    n, C = starts.shape[0], img.shape[0]
+    shape = (n, C) + crop
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=img.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != img.device or out.data_ptr() % 16:
+        raise PcrlError(f"seg_cut_patches: out must be a contiguous float32 {shape} tensor on {img.device} at a 16-byte aligned address (the kernel "
+                        f"stores 16 bytes at a time), got {out.dtype} {tuple(out.shape)} at offset {out.data_ptr() % 16}")
+    lib().call("pcrl_seg_cut_patches", img, int(img.dtype == torch.float16), starts, out, n, C, *img.shape[1:], *crop, stream_handle())
+    return out
+
+
+def seg_blend(z, starts, weights, shape, labels=None, counts=None, row=0, want_mask=True, want_probs=False, want_numden=False, want_sums=True,
+              wb=1.0, wd=1.0):
+    """The per-patch logits of ONE case z float32 [P, cx, cy, cz, K] (patches in x-major order of the per-axis `starts`, three ascending int32 device
+    vectors) blended with the separable window `weights` (three float32 device vectors of the crop's sizes) into the volume `shape` = (X, Y, Z)
+    (pcrl_seg_blend): num_k = sum w z_k and den = sum w over the covering patches in ascending order, plain float32; prediction num_k >= 0.
+    labels: uint8 [X, Y, Z] on the device or None; counts: int64 [cases, K, 3], row `row` gets {TP, |pred|, |gt|} ADDED (needs want_sums).
+    -> (mask uint8 [X, Y, Z] | None, probs float32 [K, X, Y, Z] | None, sums float64 [4 K + 1] | None, loss 0-d float32 | None,
+        numden float32 [2 K + 1, X, Y, Z] | None: num per class, then den, then zbar = num / den per class)"""
+    dev = z.device
+    if z.dim() != 5 or z.dtype != torch.float32 or not z.is_contiguous() or not z.is_cuda:
+        raise PcrlError(f"seg_blend: z must be a contiguous float32 [P, cx, cy, cz, K] tensor on the GPU, got {z.dtype} {tuple(z.shape)} on {z.device}")
+    P, cx, cy, cz, K = z.shape
+    X, Y, Z = (int(s) for s in shape)
+    for name, vs, want in (("starts", starts, torch.int32), ("weights", weights, torch.float32)):
+        if len(vs) != 3 or any(v.dtype != want or v.dim() != 1 or not v.is_contiguous() or v.device != dev for v in vs):
+            raise PcrlError(f"seg_blend: {name} must be three contiguous {want} vectors on {dev}")
+    n = [int(s.numel()) for s in starts]
+    if n[0] * n[1] * n[2] != P:
+        raise PcrlError(f"seg_blend: {P} patches against start lists of {n[0]} x {n[1]} x {n[2]}")
+    if [int(w.numel()) for w in weights] != [cx, cy, cz]:
+        raise PcrlError(f"seg_blend: the weight tables have {[int(w.numel()) for w in weights]} entries for a {cx} x {cy} x {cz} crop")
+    if not 1 <= K <= 7 or min(X, Y, Z) < 1:
+        raise PcrlError(f"seg_blend: 1 <= K <= 7 classes and a non-empty volume, got K = {K} and {X} x {Y} x {Z}")
+    V = X * Y * Z
+    if labels is not None and (labels.dtype != torch.uint8 or labels.numel() != V or not labels.is_contiguous() or labels.device != dev):
+        raise PcrlError(f"seg_blend: labels must be a contiguous uint8 bitmask of {V} voxels on {dev}, got {labels.dtype} {tuple(labels.shape)}")
+    crow = None
+    if counts is not None:
+        if counts.dtype != torch.int64 or counts.dim() != 3 or tuple(counts.shape[1:]) != (K, 3) or not counts.is_contiguous() or counts.device != dev:
+            raise PcrlError(f"seg_blend: counts must be a contiguous int64 [cases, {K}, 3] tensor on {dev}, got {counts.dtype} {tuple(counts.shape)}")
+        if not 0 <= int(row) < counts.shape[0] or not want_sums:
+            raise PcrlError(f"seg_blend: row {row} of a counts table with {counts.shape[0]} rows (counts come with the sums)")
+        crow = counts[int(row)]
+    mask = torch.empty((X, Y, Z), dtype=torch.uint8, device=dev) if want_mask else None
+    probs = torch.empty((K, X, Y, Z), dtype=torch.float32, device=dev) if want_probs else None
+    numden = torch.empty((2 * K + 1, X, Y, Z), dtype=torch.float32, device=dev) if want_numden else None
+    sums = loss = ws = None
+    nb = 0
+    if want_sums:
+        sums, loss = torch.empty(4 * K + 1, dtype=torch.float64, device=dev), _f32(1, dev)
+        nb = lib().call("pcrl_seg_blend_ws_bytes", X, Y, Z)
+        ws = workspace(nb, dev)
+    lib().call("pcrl_seg_blend", z, P, *starts, *n, *weights, cx, cy, cz, X, Y, Z, K, labels, mask, probs, numden, crow, sums, loss, wb, wd, ws, nb,
+               stream_handle())
+    return mask, probs, sums, None if loss is None else loss.view(()), numden

@@ -2,10 +2,13 @@
 
     python seg3d.py train   --data DIR --phase finetune --weights PRETRAIN.pt --n_class 3 --in_channels 4 --save_best --output OUT
     python seg3d.py predict --data DIR --list test.txt --weights OUT/pcrlv2_seg3d_finetune_1.0_best.pt --out PRED
+    python seg3d.py predict --data DIR --list test.txt --weights OUT/pcrlv2_seg3d_finetune_1.0_best.pt --out PRED --overlap 0.5 --window gaussian --probs
 
 DIR holds <case>_img.npy [C,X,Y,Z] float32 / float16, <case>_seg.npy [X,Y,Z] uint8 (bit k = class k, bit 7 = not counted) and train.txt / val.txt /
 test.txt (pcrlv2_amd/data_seg.py); `--data synthetic` trains on phantoms.  The loop is pcrlv2_amd/train_seg.py, the model models.Segmenter3d, the
-output head and its Dice/BCE loss one HIP operator (csrc/seg_head.hip).  DESIGN.md section 15.
+output head and its Dice/BCE loss one HIP operator (csrc/seg_head.hip).  DESIGN.md section 15.  `--overlap F` (predict) and `--val_overlap F` (train)
+replace the stride-tiled patches by overlapping windows blended with a centre-weighted window (csrc/seg_blend.hip); 0, the
+default, is the tiled path.
 """
 from __future__ import annotations
 
@@ -26,6 +29,9 @@ def check_train(args):
         raise SystemExit("--phase scratch starts from random weights: drop --weights or use --phase finetune")
     if args.b < 1 or args.epochs < 1 or args.steps_per_epoch < 0:
         raise SystemExit("--b and --epochs must be positive, --steps_per_epoch non-negative")
+    from .data_seg import check_overlap, check_window
+    check_overlap(args.val_overlap, "--val_overlap")
+    check_window(args.val_window, "--val_window")
 
 
 def train(args):
@@ -36,11 +42,20 @@ def train(args):
     return train_segmenter(args)
 
 
-def predict(args):
-    from .data_seg import parse_crop
+def check_predict(args):
+    """Every refused combination exits with its message, before anything touches a GPU."""
+    from .data_seg import check_overlap, check_window, parse_crop
     parse_crop(args.crop)
     if args.b < 1:
         raise SystemExit("--b must be positive")
+    check_window(args.window)
+    if check_overlap(args.overlap) == 0 and args.probs:
+        raise SystemExit("--probs writes the blended probabilities of overlapping windows: it needs --overlap > 0 (the tiled path thresholds its logits "
+                         "inside the kernel)")
+
+
+def predict(args):
+    check_predict(args)
     from .train_seg import predict as run
     return run(args)
 
@@ -69,6 +84,9 @@ def build_parser():
     tr.add_argument("--seed", type=int, default=42)
     tr.add_argument("--steps_per_epoch", type=int, default=0, help="batches per epoch; 0 = one crop per training case")
     tr.add_argument("--workers", type=int, default=4)
+    tr.add_argument("--val_overlap", type=float, default=0.0, help="validation and the final test by sliding windows that overlap by this fraction of "
+                    "the crop, blended (0..0.75); 0 = stride-tiled patches")
+    tr.add_argument("--val_window", default="gaussian", help="blending window with --val_overlap > 0: gaussian | constant")
     tr.set_defaults(model="pcrlv2", n="seg3d", ratio=1.0)
     pr = sub.add_parser("predict", help="write <case>_pred.npy (uint8 bitmask) for every case of a list")
     pr.add_argument("--data", required=True, help="directory with <case>_img.npy")
@@ -79,6 +97,10 @@ def build_parser():
     pr.add_argument("--b", type=int, default=8, help="patches per forward")
     pr.add_argument("--amp", action="store_true")
     pr.add_argument("--gpu", type=int, default=0)
+    pr.add_argument("--overlap", type=float, default=0.0, help="sliding windows that overlap by this fraction of the crop, blended (0..0.75); 0 = "
+                    "stride-tiled patches, every voxel from one patch")
+    pr.add_argument("--window", default="gaussian", help="blending window with --overlap > 0: gaussian | constant")
+    pr.add_argument("--probs", action="store_true", help="with --overlap > 0: also write <case>_prob.npy, float16 [K, X, Y, Z]")
     return ap
 
 

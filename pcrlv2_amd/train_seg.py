@@ -5,6 +5,9 @@ The reference's fine-tune branch is not public.  What is pinned: the model (mode
 checkpoint loads into the reference's class) and the optimiser / schedule of its 3D pre-training (SGD, cosine).  This project's own choices: the loss
 wb * BCE + wd * (1 - mean Dice) on overlapping sigmoid regions, mean per-case Dice as the metric, crops and stride-tiled evaluation (data_seg).
 
+With --overlap / --val_overlap > 0 a case is predicted by overlap-blended sliding windows instead (sliding_window: patches cut on the device, the head's
+logits kept per case, one blend kernel); at 0, the default, everything below is the tiled path.
+
 The run, the epoch and the bracket around a step are pcrlv2_amd.loop's; validation is ONE pass of Segmenter3d.infer over the tiles with the integer
 counts {TP, |pred|, |gt|} per (case, class) and the loss sums kept on the device, one all_reduce of both when there is a process group (cases are
 sharded by rank, every rank indexes the global case table) and one host read-back.
@@ -20,6 +23,7 @@ import torch.distributed as dist
 
 from . import data_seg as _data
 from . import loop as _loop
+from . import ops as _ops
 from .loop import to_gpu
 from .models import Segmenter3d
 from .optim import FusedSGD
@@ -91,6 +95,68 @@ def _fmt(val):
     return 'loss {0:.4f}\tmean Dice {1:.4f}\t({2} cases)'.format(val["loss"], val["mean_dice"], val["cases"])
 
 
+# ---- overlap-blended sliding windows ----------------------------------------------------------------------------------------------
+def sliding_window(model, case, crop, b, overlap, window, *, counts=None, row=0, want_mask=True, want_probs=False, max_bytes=16 << 30):
+    """One case by overlapping crop-sized windows (data_seg.windows) whose logits are blended with a centre-weighted window (data_seg.blend_weights):
+    the image (and the labels, when the case has them) is uploaded once, `b` patches per forward are cut on the device (ops.seg_cut_patches),
+    model.infer_logits writes into the per-case buffer [P, *crop, K], and ONE ops.seg_blend call turns it into the prediction; with labels, row `row`
+    of `counts` gets {TP, |pred|, |gt|} added.  -> (mask uint8 [X, Y, Z] | None, probs float32 [K, X, Y, Z] | None, sums float64 [4 K + 1]), on the
+    device; an unlabelled case without `counts` has nothing to sum: its sums are None and the blend runs without them.  A buffer above `max_bytes` is refused before anything is uploaded."""
+    crop, K, b = tuple(int(c) for c in crop), int(model.n_class), int(b)
+    axes = _data.windows(case.shape, crop, overlap)
+    weights = _data.blend_weights(crop, window)
+    starts = _data.window_starts(axes)
+    P = len(starts)
+    nbytes = P * crop[0] * crop[1] * crop[2] * K * 4
+    if nbytes > max_bytes:
+        raise SystemExit(f"{case.name}: the logits of its {P} patches at overlap {overlap:g} need {nbytes / 2 ** 30:.1f} GiB, above the limit of "
+                         f"{max_bytes / 2 ** 30:.1f} GiB for one case: use a smaller --overlap")
+    dev = next(model.parameters()).device
+    img = torch.from_numpy(np.ascontiguousarray(case.img)).to(dev)
+    labels = None if case.seg is None else torch.from_numpy(np.ascontiguousarray(case.seg)).to(dev)
+    st = torch.tensor(starts, dtype=torch.int32, device=dev)
+    z = torch.empty((P,) + crop + (K,), dtype=torch.float32, device=dev)
+    for a in range(0, P, b):
+        model.infer_logits(_ops.seg_cut_patches(img, st[a:a + b], crop), out=z[a:a + b])
+    mask, probs, sums, _, _ = _ops.seg_blend(z, [torch.tensor(a, dtype=torch.int32, device=dev) for a in axes], [torch.from_numpy(w).to(dev) for w in weights],
+                                             case.shape, labels=labels, counts=counts, row=row, want_mask=want_mask, want_probs=want_probs,
+                                             want_sums=labels is not None or counts is not None, wb=model.wb, wd=model.wd)
+    return mask, probs, sums
+
+
+class _CaseShard:
+    """This rank's contiguous shard of a case table as the `loader` of loop.held_out_pass: one case index (into the GLOBAL table) per step."""
+    sharded = True
+
+    def __init__(self, n, rank, world):
+        self.mine = range(rank * n // world, (rank + 1) * n // world)
+
+    def __iter__(self):
+        return iter(self.mine)
+
+
+def evaluate_sliding(model, cases, crop, b, overlap, window, rank=0, world=1, group=None):
+    """`evaluate` with every case predicted by sliding_window: the same dictionary from the same ONE held_out_pass, one all_reduce of sums and counts
+    and one host read-back.  The sums of the cases add up (they are sums over counted voxels), so the loss is the pass's, as in `evaluate`."""
+    dev = next(model.parameters()).device
+    K, n_cases = model.n_class, len(cases)
+    ns = 4 * K + 1
+    counts = torch.zeros((max(n_cases, 1), K, 3), dtype=torch.int64, device=dev)
+    acc = torch.zeros(ns + n_cases * K * 3, dtype=torch.float64, device=dev)
+
+    def per_case(ci):
+        acc[:ns] += sliding_window(model, cases[ci], crop, b, overlap, window, counts=counts, row=ci, want_mask=False)[2]
+
+    def counts_into_acc():
+        acc[ns:] = counts[:n_cases].reshape(-1).double()
+        return acc.new_zeros(0)
+
+    host = _loop.held_out_pass(_CaseShard(n_cases, rank, world), group, acc, per_case, also_read=counts_into_acc)
+    table = [[[int(v) for v in host[ns + (c * K + k) * 3:ns + (c * K + k) * 3 + 3]] for k in range(K)] for c in range(n_cases)]
+    per, mean = dice_from_counts(table)
+    return {"loss": loss_from_sums(host[:ns], K, model.wb, model.wd) if n_cases else float("nan"), "dice": per, "mean_dice": mean, "cases": n_cases}
+
+
 def resume_segmenter(path, model, optimizer, rank):
     ckpt = torch.load(path, map_location="cpu", weights_only=False)
     model.load_state_dict(ckpt["state_dict"])
@@ -107,6 +173,13 @@ def train_segmenter(args):
 def _train_segmenter(args, distributed):
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     loaders = _data.loaders(args, rank, world)
+    overlap, window = float(getattr(args, "val_overlap", 0.0)), getattr(args, "val_window", "gaussian")
+    crop = _data.parse_crop(args.crop)
+    if overlap > 0:          # validation and the final test by overlap-blended sliding windows; 0 (the default): the tiled pass
+        held_out = lambda model, loader: evaluate_sliding(model, loader.cases, crop, args.b, overlap, window, rank, world)      # noqa: E731
+        tail = "\toverlap {0:g} {1}".format(overlap, window)
+    else:
+        held_out, tail = evaluate, ""
 
     def make(rank):
         return Segmenter3d(args.n_class, in_channels=args.in_channels, weights=args.weights if args.phase == "finetune" else None)
@@ -119,8 +192,8 @@ def _train_segmenter(args, distributed):
         state_dict=lambda model: model.state_dict(),
         epoch=lambda epoch, loader, model, optimizer, verbose: _loop.run_epoch(epoch, loader, model, lambda batch: train_step(model, optimizer, batch),
                                                                                (("seg loss", 0),), verbose),
-        validate=lambda model, loader, epoch: evaluate(model, loader),
-        val_text=_fmt, better=higher_dice, best_keys=('epoch', 'state_dict', 'val'),
+        validate=lambda model, loader, epoch: held_out(model, loader),
+        val_text=lambda val: _fmt(val) + tail, better=higher_dice, best_keys=('epoch', 'state_dict', 'val'),
         val_every_0_is_1=True, save_last=True)
     model, last_epoch, chatty = _loop.run_epochs(args, loaders, task, distributed)
     if last_epoch is not None:       # the final test: the best model by validation Dice when one was kept, otherwise the last epoch's
@@ -132,9 +205,9 @@ def _train_segmenter(args, distributed):
             ckpt = torch.load(best_file, map_location="cpu", weights_only=False)
             model.load_state_dict(ckpt["state_dict"])
             which = "best epoch %d" % ckpt["epoch"]
-        test = evaluate(model, loaders['test'])
+        test = held_out(model, loaders['test'])
         if chatty:
-            print('Test: ({0})\t{1}\tper class {2}'.format(which, _fmt(test), " ".join("%.4f" % d for d in test["dice"])))
+            print('Test: ({0})\t{1}\tper class {2}{3}'.format(which, _fmt(test), " ".join("%.4f" % d for d in test["dice"]), tail))
             sys.stdout.flush()
         model.test_metrics = test
     return model
@@ -168,6 +241,7 @@ def predict_case(model, case, crop, b):
 
 def predict(args, log=print):
     crop = _data.parse_crop(args.crop)
+    overlap, window, want_probs = float(getattr(args, "overlap", 0.0)), getattr(args, "window", "gaussian"), bool(getattr(args, "probs", False))
     device = torch.device("cuda", args.gpu)
     torch.cuda.set_device(device)
     model = load_segmenter(args.weights, device, args.amp)
@@ -176,6 +250,12 @@ def predict(args, log=print):
     for name in names:
         case = _data.open_case(args.data, name, model.n_class, model.in_channels, need_seg=False)
         case.seg = None          # the prediction does not look at labels
-        np.save(os.path.join(args.out, name + "_pred.npy"), predict_case(model, case, crop, args.b))
+        if overlap > 0:
+            mask, probs, _ = sliding_window(model, case, crop, args.b, overlap, window, want_probs=want_probs)
+            np.save(os.path.join(args.out, name + "_pred.npy"), mask.cpu().numpy())
+            if want_probs:
+                np.save(os.path.join(args.out, name + "_prob.npy"), probs.half().cpu().numpy())
+        else:
+            np.save(os.path.join(args.out, name + "_pred.npy"), predict_case(model, case, crop, args.b))
     log(f"[seg3d] {len(names)} masks written to {args.out}")
     return len(names)
