@@ -552,14 +552,17 @@ int pcrl_sgd_step_guarded(float* p, const float* g, float* buf, const int64_t* o
 
 /* ---------------------------------------------------------------------------------------
  * Input pipeline: the torchio transforms of data.py:73-89 / datasets/lunaDataset.py:28-81 on float32 volumes
- * [B][D][H][W] resident on the device, one random parameter set per volume (drawn by the caller).  PARITY UNPINNED against torchio
- * (absent from the image; the reference holds no vectors); each entry point states the definition it implements.
+ * [B][D][H][W] resident on the device, one random parameter set per volume (drawn by the caller).  Each entry point states the definition
+ * it implements and is pinned to it alone, bit for bit or to a derived bound (tests/test_augment_exact_gpu.py); the blur's definition is held
+ * to scipy.ndimage.gaussian_filter within the tail mass of its fixed radius.  NOT PINNED: torchio itself (absent from the image; the
+ * reference holds no vectors) -- its affine conventions and random streams.  Every entry point refuses null pointers, B <= 0, empty
+ * extents (and B > 65535 where B is the grid's y: affine, blur_axis, noise_gamma, znorm); affine and blur_axis refuse x == y.
  *   volume_min : vmin[b] = min over the volume (RandomAffine's default_pad_value='minimum')
  *   affine     : RandomFlip(axes=0) then RandomAffine: y(o) = trilinear sample of flip_d^{flip[b]}(x) at centre + inv[b] (o - centre),
  *                inv[b] row-major 3x3 in (d,h,w) order and isotropic voxel units, samples outside the volume = fill[b]
  *   blur_axis  : one axis (0=d,1=h,2=w) of RandomBlur: Gaussian of std sigma[b] voxels, taps -radius..radius, symmetric borders
- *   noise_gamma: RandomNoise then RandomGamma: v = x + noise_std[b] * n(0,1) (counter-based generator keyed by seed, b, index),
- *                y = sign(v) |v|^gamma[b]
+ *   noise_gamma: RandomNoise then RandomGamma: v = x + noise_std[b] * n(0,1) (counter-based generator: index, volume and all 64 seed bits
+ *                key both Box-Muller draws through two per-volume keys, so no two volumes of a call share a field), y = sign(v) |v|^gamma[b]
  *   meanstd / znorm : ZNormalization: (x - mean[b]) * rstd[b], rstd = 1 / unbiased standard deviation
  *   swap       : RandomSwap, in place: for it < iters, exchange patch origins[it][b][0] with patch origins[it][b][1] ([d,h,w] corners,
  *                patch pd x ph x pw); the caller makes the two corners of a skipped (overlapping) draw equal */

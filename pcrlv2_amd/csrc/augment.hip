@@ -9,9 +9,16 @@
 //   ZNormalization                                                                     -> pcrl_aug_meanstd + pcrl_aug_znorm
 //
 // All kernels are HBM/latency-bound streaming kernels over tensors of a few MB (64 global crops of 512 KB + 192 local crops of
-// 16 KB per b = 32 batch); coalesced along w, per-volume coefficients in registers / LDS.  PARITY UNPINNED against torchio (not
-// installed in the image; the reference holds no vectors): the kernels follow torchio's documented behaviour and are tested
-// against a float64 PyTorch restatement of the same definitions (tests/test_augment_gpu.py).
+// 16 KB per b = 32 batch); coalesced along w, per-volume coefficients in registers / LDS.
+//
+// PINNED (tests/test_augment_exact_gpu.py, case table and derivations in tests/aug_cases.py): every kernel alone against its definition, at
+// the sizes where its loops turn over -- volume_min, affine (dyadic lattice), znorm, swap and the identity passes of the blur bit for bit; the
+// blur to a derived float32 bound; the integer hash of the noise bit for bit and the deviate / gamma map to 4 x a float32 evaluation (logf,
+// cosf, powf are the device library's); mean exactly and rstd to the one-pass formula's double round-off plus one float32 rounding; every
+// refusal of every entry point.  The blur's definition (radius 8, renormalised) equals scipy.ndimage.gaussian_filter (truncate 4 sigma,
+// reflect) up to the tail mass the fixed radius keeps: at most 4.9e-5 of the data range per axis (tests/test_aug_cases_cpu.py).
+// NOT PINNED: torchio itself (not installed; the reference holds no vectors) -- its affine conventions and its random streams.  The kernels
+// follow torchio's documented behaviour; the chain as a whole is tested against a float64 restatement in tests/test_augment_gpu.py.
 #include "common.h"
 
 namespace {
@@ -97,14 +104,21 @@ __global__ void __launch_bounds__(256) blur_axis_kernel(const float* __restrict_
   y[b * S + i] = acc / norm;
 }
 
-// ---- counter-based normal deviates: two rounds of an integer hash -> Box-Muller ----
+// ---- counter-based normal deviates: an integer hash of (seed, volume, index), no state -> Box-Muller ----
+// Two per-volume keys (wave-uniform): k0 from the seed's low word permutes the index, k1 from its high word is ADDED after the first mixing
+// round.  With k0 alone the volume was a pure XOR on the index: two volumes with (k0_i ^ k0_j) < S (S a power of two) drew the same field,
+// permuted by idx ^ K -- about one call in sixteen at 64 volumes of 2^17.  For one seed k1 is a bijection of the volume, so two volumes of a
+// call never hold both keys in common, and the sets {mix32(idx ^ k0_i)} + k1_i differ (tests/test_aug_cases_cpu.py searches seeds 0 .. 4095
+// x 256 volumes).  Both draws depend on the index, the volume and all 64 seed bits.  One mix32 per element more than before (four).
 __device__ __forceinline__ uint32_t mix32(uint32_t v) {
   v ^= v >> 16; v *= 0x7feb352du; v ^= v >> 15; v *= 0x846ca68bu; v ^= v >> 16;
   return v;
 }
 __device__ __forceinline__ float normal_at(uint64_t seed, uint32_t vol, uint64_t idx) {
   const uint32_t k0 = mix32((uint32_t)seed ^ mix32(vol * 0x9e3779b9u + 0x85ebca6bu));
-  const uint32_t a = mix32((uint32_t)idx ^ k0), b2 = mix32((uint32_t)(idx >> 32) + 0x632be5abu + a ^ (uint32_t)(seed >> 32));
+  const uint32_t k1 = mix32((uint32_t)(seed >> 32) ^ mix32(vol * 0x85ebca6bu + 0xc2b2ae35u));
+  const uint32_t a = mix32(mix32((uint32_t)idx ^ k0) + k1);
+  const uint32_t b2 = mix32(((uint32_t)(idx >> 32) + 0x632be5abu + a) ^ k1);
   const uint32_t c = mix32(a + 0x9e3779b9u + b2);
   const float u1 = ((float)(a >> 8) + 1.0f) * (1.0f / 16777216.0f);   // (0, 1]
   const float u2 = (float)(c >> 8) * (1.0f / 16777216.0f);            // [0, 1)
@@ -203,7 +217,7 @@ extern "C" int pcrl_aug_affine(const float* x, float* y, const float* inv, const
 extern "C" int pcrl_aug_blur_axis(const float* x, float* y, const float* sigma, int B, int D, int H, int W, int axis, int radius,
                                   pcrl_stream_t stream) {
   PCRL_REQUIRE(x && y && sigma && x != y, "aug_blur_axis: null pointer or in-place call");
-  PCRL_REQUIRE(B > 0 && B <= 65535 && axis >= 0 && axis < 3 && radius >= 0 && radius <= 32, "aug_blur_axis: bad arguments");
+  PCRL_REQUIRE(B > 0 && B <= 65535 && D > 0 && H > 0 && W > 0 && axis >= 0 && axis < 3 && radius >= 0 && radius <= 32, "aug_blur_axis: bad arguments");
   const int64_t S = (int64_t)D * H * W;
   hipLaunchKernelGGL(blur_axis_kernel, dim3((unsigned)((S + 255) / 256), B), dim3(256), 0, as_stream(stream), x, y, sigma, D, H, W, axis, radius);
   return pcrl_check_launch("aug_blur_axis");

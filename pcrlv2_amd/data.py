@@ -11,11 +11,19 @@ z-normalisation run batched on the device on the raw crops.
 The transforms are hand-written gfx950 kernels (csrc/augment.hip, `pcrl_aug_*` in include/pcrl_hip.h); only the per-volume random
 parameters are drawn with torch.
 
-PARITY UNPINNED.  torchio is not installed in the build image and the reference holds no vectors for its augmentations, so these
-are restatements of torchio's documented defaults (RandomFlip(axes=0, p=0.5); RandomAffine(scales 0.9-1.1, degrees +-10 per axis,
+PARITY WITH TORCHIO UNPINNED.  torchio is not installed in the build image and the reference holds no vectors for its augmentations, so
+these are restatements of torchio's documented defaults (RandomFlip(axes=0, p=0.5); RandomAffine(scales 0.9-1.1, degrees +-10 per axis,
 linear, pad with the image minimum); RandomBlur(std 0-2 per axis); RandomNoise(std 0-0.25); RandomGamma(log_gamma +-0.3);
-RandomSwap(patch (8,4,4), 100 iterations); ZNormalization), tested against a float64 PyTorch restatement of the same definitions
-(tests/aug_reference.py, tests/test_augment_gpu.py) and for their defining properties, not against torchio.  The batch contract -- (input1, input2, gt, gt2, [6 local views]), gt = the spatially transformed crop BEFORE the
+RandomSwap(patch (8,4,4), 100 iterations); ZNormalization).
+Pinned: each kernel to its definition, alone, bit for bit or to a derived bound (tests/aug_cases.py, tests/test_augment_exact_gpu.py), the
+chain as a whole against a float64 restatement (tests/aug_reference.py, tests/test_augment_gpu.py), `draw_swap`'s overlap rule, and the
+blur's definition against scipy.ndimage.gaussian_filter(truncate=4, mode="reflect"), which torchio's RandomBlur is understood to call.
+Known deviation of the blur from scipy's: the kernel always takes radius BLUR_RADIUS = 8 and renormalises, scipy truncates at
+int(4 sigma + 0.5) taps; the two differ by at most the discarded tail mass 2 sum_{R(sigma) < t <= 8} w(t) / sum w per axis times the data
+range -- at most 4.9e-5 per axis (sigma just under 1.625), 3.7e-5 measured over three axes on uniform data (tests/test_aug_cases_cpu.py).
+Not pinned: torchio's affine conventions (axis order, centre, interpolation at the border) and its random streams.
+The noise is a counter hash of (index, volume, 64-bit seed) with two per-volume keys: no two volumes of a call share a field.
+The batch contract -- (input1, input2, gt, gt2, [6 local views]), gt = the spatially transformed crop BEFORE the
 intensity transforms (lunaDataset.py:37-41) -- is the reference's.
 """
 from __future__ import annotations

@@ -5,12 +5,13 @@ Not used by the product path."""
 import torch
 
 
-def ref_spatial(x, flip, inv):
-    """flip along d where flip[b], then resample: y(o) = trilinear sample at centre + inv[b] (o - centre), outside = volume minimum."""
+def ref_spatial(x, flip, inv, fill=None):
+    """flip along d where flip[b], then resample: y(o) = trilinear sample at centre + inv[b] (o - centre), outside = `fill[b]` (default: the
+    volume minimum)."""
     B, D, H, W = x.shape
     x = x.double()
     x = torch.where(flip.view(-1, 1, 1, 1).bool(), x.flip(1), x)
-    fill = x.amin(dim=(1, 2, 3))
+    fill = x.amin(dim=(1, 2, 3)) if fill is None else fill.double()
     dev = x.device
     d, h, w = torch.meshgrid(torch.arange(D, device=dev), torch.arange(H, device=dev), torch.arange(W, device=dev), indexing="ij")
     c = torch.stack([d + 0.5 - D / 2, h + 0.5 - H / 2, w + 0.5 - W / 2], 0).double().view(1, 3, -1)          # [1,3,S]
