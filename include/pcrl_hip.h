@@ -132,6 +132,7 @@ int pcrl_conv3d_k3_c1_wgrad(const float* x, const void* dy, float* dw_ref, void*
 
 /* Convolutions with ONE output channel: deep-supervision head conv3x3x3 C->1 (pcrlv2_model_3d.py:60,71)
  * and OutputTransition.final_conv 1x1x1 64->1 (:78).  taps = 27 or 1.  y, dy: float32 [M].
+ * C: a multiple of 8 (bf16) / 4 (float32), <= 1024, and taps * C * 4 <= 65536 bytes (27 taps: C <= 606) -- fwd and dgrad keep the weights in LDS.
  * w_ref: [1][C][taps] float32.  `stats_partial`: [pcrl_conv3d_to1_stats_rows(...)][1][2] or NULL.  fwd, 27 taps, three kernels:
  * an LDS-halo brick kernel (bf16, D%4 == 0, H%8 == 0, W%8 == 0, C%32 == 0: z = x.w for every halo voxel on MFMA, gathered per
  * output voxel inside the block; one statistics row per 4x8x8 brick); else a pointwise MFMA product z[t][m] = sum_c x[m][c] w[c][t]
@@ -149,6 +150,7 @@ int pcrl_conv3d_to1_dgrad(const float* dy, const float* w_ref, const void* add_s
 size_t pcrl_conv3d_to1_wgrad_ws_bytes(int N, int D, int H, int W, int C, int taps);
 int pcrl_conv3d_to1_wgrad(const void* x, const float* dy, float* dw_ref, float* db, void* ws, size_t ws_bytes,
                           int N, int D, int H, int W, int C, int taps, int dtype, pcrl_stream_t stream);
+int64_t pcrl_conv3d_to1_wgrad_route(int D, int H, int W, int C, int taps, int dtype);   /* informational: 0 im2col + plain GEMM, 1 scalar brick kernel, 2 weighted column sum (1 tap) */
 
 /* ---------------------------------------------------------------------------------------
  * ConvTranspose3d kernel 2 stride 2 -- aten::convolution (transposed) at pcrlv2_model_3d.py:52,64.
@@ -161,6 +163,8 @@ int pcrl_convt3d_k2s2_dgrad(const void* dy, const void* wp_dgrad, void* dx,
 size_t pcrl_convt3d_k2s2_wgrad_ws_bytes(int N, int D, int H, int W, int Ci, int Co);
 int pcrl_convt3d_k2s2_wgrad(const void* x, const void* dy, float* dw_ref, void* ws, size_t ws_bytes,
                             int N, int D, int H, int W, int Ci, int Co, int dtype, pcrl_stream_t stream);
+int64_t pcrl_convt3d_k2s2_fwd_kernel(int Ci, int Co, int dtype);    /* informational: 1 streaming kernel (conv_up2.hip), 0 implicit GEMM */
+int64_t pcrl_convt3d_k2s2_wgrad_route(int Ci, int Co, int dtype);   /* informational: 1 all-taps kernel, 0 gather kernel */
 
 /* Per-channel column sum of a [M][C] activation (bias gradients): out[c] = sum_m v[m][c].
  * ws: pcrl_colsum_ws_bytes(M, C). */

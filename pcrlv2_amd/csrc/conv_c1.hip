@@ -403,7 +403,7 @@ __global__ void __launch_bounds__(256) to1_dgrad_kernel(const float* __restrict_
       const float dv = dy[m];
       const float* wr = wl + cv * VEC;
 #pragma unroll
-      for (int j = 0; j < VEC; ++j) acc[j] = dv * wr[j];
+      for (int j = 0; j < VEC; ++j) acc[j] += dv * wr[j];   // 0 + product, as the 27-tap loop starts: a product of -0 stores +0, the sign aten's gradient has
     }
     T* o = dx + m * C + cv * VEC;
     Vec16<T> ov;
@@ -528,6 +528,8 @@ static int to1_check(const char* what, int C, int taps, int dtype) {
   const int vec = dtype == PCRL_BF16 ? 8 : 4;
   if (dtype != PCRL_BF16 && dtype != PCRL_F32) return pcrl_fail(PCRL_EINVAL, "%s: bad dtype %d", what, dtype);
   if (C <= 0 || C % vec != 0 || C > 1024) return pcrl_fail(PCRL_EINVAL, "%s: C=%d must be a multiple of %d, <= 1024", what, C, vec);
+  // to1_fwd_kernel and to1_dgrad_kernel keep the weights [taps][C] as float32 in dynamic LDS and ask for no more than the 64 KiB a launch gets without opting in
+  if ((size_t)taps * C * sizeof(float) > 65536) return pcrl_fail(PCRL_EINVAL, "%s: taps * C = %d * %d float32 weights exceed 64 KiB of LDS (27 taps: C <= 606)", what, taps, C);
   return 0;
 }
 

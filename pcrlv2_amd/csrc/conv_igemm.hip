@@ -688,11 +688,15 @@ extern "C" int pcrl_conv3d_k3_dgrad_bnred(const void* dy, const void* wp_dgrad, 
   return pcrl_brick16_dgrad_bnred_launch(dy, wp_dgrad, dx, bn_y, scale, shift, mean, rstd, partial, N, D, H, W, Ci, Co, as_stream(stream));
 }
 
+// the streaming kernel (conv_up2.hip) takes this shape
+static bool convt_up2_route(int Ci, int Co, int dtype) { return g_hooks.conv_impl == 0 && pcrl_convt_up2_eligible(Ci, Co, dtype); }
+extern "C" int64_t pcrl_convt3d_k2s2_fwd_kernel(int Ci, int Co, int dtype) { return convt_up2_route(Ci, Co, dtype) ? 1 : 0; }
+
 extern "C" int pcrl_convt3d_k2s2_fwd(const void* x, const void* wp_fwd, const float* bias, void* y,
                                      int N, int D, int H, int W, int Ci, int Co, int dtype, pcrl_stream_t stream) {
   if (int e = check_dims("convt3d_k2s2_fwd", N, D, H, W, Ci, Co)) return e;
   PCRL_REQUIRE(x && wp_fwd && y, "convt3d_k2s2_fwd: null pointer");
-  if (g_hooks.conv_impl == 0 && pcrl_convt_up2_eligible(Ci, Co, dtype))
+  if (convt_up2_route(Ci, Co, dtype))
     return pcrl_convt_up2_launch(x, wp_fwd, bias, y, N, D, H, W, Ci, Co, as_stream(stream));
   IgemmParams p{x, wp_fwd, bias, y, nullptr, Dims{N, D, H, W}, (int64_t)N * D * H * W, Ci, Co, 1, nullptr, 0};
   return dispatch<GEOM_UP2_FWD>(p, 8, dtype, as_stream(stream));

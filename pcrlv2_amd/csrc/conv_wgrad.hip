@@ -1316,6 +1316,9 @@ static ScalarWgradRoute scalar_wgrad_route(int D, int H, int W, int C, int taps,
   if (scalar_brick_ok(D, H, W, C, taps, dtype)) return SCALAR_WG_BRICK;
   return taps == 1 && C % (dtype == PCRL_BF16 ? 8 : 4) == 0 && C <= 512 ? SCALAR_WG_POINTWISE : SCALAR_WG_PLAIN;
 }
+// informational: the route a shape gets under the current hooks
+extern "C" int64_t pcrl_conv3d_to1_wgrad_route(int D, int H, int W, int C, int taps, int dtype) { return scalar_wgrad_route(D, H, W, C, taps, dtype); }
+extern "C" int64_t pcrl_convt3d_k2s2_wgrad_route(int Ci, int Co, int dtype) { return convt_wgrad_route(Ci, Co, dtype); }
 
 extern "C" size_t pcrl_conv3d_k3_wgrad_ws_bytes(int N, int D, int H, int W, int Ci, int Co) {
   const SplitPlan sp = plan_splits((int64_t)N * D * H * W, Co, Ci, 27);

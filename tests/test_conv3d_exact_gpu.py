@@ -3,8 +3,9 @@ is tests/test_conv2d_exact_gpu.py, which explains the method).  pcrl_conv3d_k3_f
 under every conv test-hook code defined for the shape, pcrl_conv3d_k3_fwd_affine, the first layer (pcrl_conv3d_k3_c1_fwd, _c1_fwd_affine, _c1_wgrad)
 and pcrl_conv3d_k3_wgrad under the impl / tr pairs of tests/test_ops_gpu.py::test_conv3d_fwd_stats_dgrad_wgrad.
 
-Out of scope here: the composed up-convolution (its phase weights are float32 sums of products and leave the lattice; tests/test_mfma_pin_gpu.py owns
-it), the one-channel convolutions, the transposed convolution, BatchNorm and the losses."""
+The one-channel convolutions and the transposed convolution are pinned the same way by tests/test_conv_to1_exact_gpu.py and
+tests/test_convt_exact_gpu.py (cases: tests/conv1_cases.py).  Out of scope of the lattice method: the composed up-convolution (its phase weights are
+float32 sums of products and leave the lattice; tests/test_mfma_pin_gpu.py owns it)."""
 import collections
 import functools
 import types
