@@ -809,6 +809,36 @@ int pcrl_seg_blend(const float* z, int64_t P, const int* sx, const int* sy, cons
                    const float* wz, int cx, int cy, int cz, int X, int Y, int Z, int K, const uint8_t* labels, uint8_t* mask, float* probs, float* numden,
                    int64_t* counts, double* sums, float* loss, float wb, float wd, void* ws, size_t ws_bytes, pcrl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * 3D path, surface-distance metrics of stored segmentation masks: HD95, HD, ASSD (csrc/surface_dist.hip, compiled with -ffp-contract=off).
+ *   Masks are the uint8 bitmasks of the segmenter, [X][Y][Z]: bit k = class k, bit 7 of the GROUND TRUTH = the voxel is not counted and belongs to
+ *   neither mask.  The definitions are MedPy's hd95 / hd / assd; the host finishes them in float64 (train_seg.surface_metrics).
+ * pcrl_surf_extract -- surf_pred, surf_gt uint8 [X][Y][Z]: bit k = the voxel is in class k's mask and at least one of its 6 face neighbours is not
+ *   (a neighbour outside the volume is not): m & ~binary_erosion(m, 6-connected cross), all K classes of both masks in one pass; bits >= K are 0.
+ *   counts int64 [K][3]: {TP, |pred|, |gt|} of the effective masks ADDED to this row (pcrl_seg_head_eval's convention; 64-bit integer atomics).
+ * pcrl_edt_sq -- d2 float64 [X][Y][Z]: the squared distance of every voxel to the nearest voxel whose byte in `surf` has bit `bit` set,
+ *       d2 = min over surface voxels of fl(fl(fl(sx dx))^2 + fl(fl(fl(sy dy))^2 + fl(fl(sz dz))^2))     float64, no fused multiply-add, this order
+ *   by three in-place line passes Z, Y, X (each min_j fl(fl(s (i - j))^2) + f[j], with an early exit that leaves every bit as it is); +inf
+ *   everywhere for an empty surface.  steps int64 [1] or NULL: the scan steps executed (two multiplications, up to two additions and three
+ *   comparisons each) are ADDED to it.  An axis may have at most pcrl_edt_max_axis() = 1024 voxels (a line is staged in LDS): PCRL_EINVAL beyond.
+ *   ws: pcrl_edt_sq_ws_bytes (0 today: ws may be NULL).
+ * pcrl_surf_dist_stats -- one class: A = d2_to_gt at the voxels of surf_pred with bit `bit`, B = d2_to_pred at those of surf_gt, U = A u B as a
+ *   multiset of n = n_a + n_b values.  record: 8 slots of 8 bytes
+ *       [0] n_a  [1] n_b  [2] lo = floor(q (double)(n - 1))                        int64
+ *       [3] [4] [5] the order statistics of d2 over U at ranks lo, min(lo + 1, n - 1), n - 1   float64, EXACT (a radix select on the bit patterns)
+ *       [6] sum of sqrt(d2) over A  [7] over B                                      float64, per-block partials added in block order
+ *   Slots 2..7 are written only when both surfaces are non-empty.  Integer atomics only: two runs give identical bytes.  0 <= q <= 1.
+ *   ws: pcrl_surf_dist_stats_ws_bytes(V), 8-byte aligned; V = X * Y * Z. */
+int pcrl_surf_extract(const uint8_t* pred, const uint8_t* gt, uint8_t* surf_pred, uint8_t* surf_gt, int64_t* counts, int X, int Y, int Z, int K,
+                      pcrl_stream_t stream);
+int64_t pcrl_edt_max_axis(void);
+size_t pcrl_edt_sq_ws_bytes(int X, int Y, int Z);
+int pcrl_edt_sq(const uint8_t* surf, int bit, double* d2, double sx, double sy, double sz, int64_t* steps, void* ws, size_t ws_bytes, int X, int Y,
+                int Z, pcrl_stream_t stream);
+size_t pcrl_surf_dist_stats_ws_bytes(int64_t V);
+int pcrl_surf_dist_stats(const double* d2_to_gt, const uint8_t* surf_pred, const double* d2_to_pred, const uint8_t* surf_gt, int bit, double q,
+                         int64_t* record, void* ws, size_t ws_bytes, int64_t V, pcrl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

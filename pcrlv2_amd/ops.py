@@ -1790,3 +1790,100 @@ def seg_blend(z, starts, weights, shape, labels=None, counts=None, row=0, want_m
     lib().call("pcrl_seg_blend", z, P, *starts, *n, *weights, cx, cy, cz, X, Y, Z, K, labels, mask, probs, numden, crow, sums, loss, wb, wd, ws, nb,
                stream_handle())
     return mask, probs, sums, None if loss is None else loss.view(()), numden
+
+
+# ----------------------------------------------------------------------------------------------
+# surface-distance metrics of stored masks: surfaces, exact squared distance transform, order statistics (csrc/surface_dist.hip)
+# ----------------------------------------------------------------------------------------------
+SURF_REC = 8      # slots of a pcrl_surf_dist_stats record: n_a, n_b, lo (int64) | d2 at lo, hi, n - 1 | sum_a, sum_b (float64 bit patterns)
+
+
+def _surf_mask(t, what, dev=None, shape=None):
+    if (not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 3 or not t.is_contiguous() or not t.is_cuda or t.numel() == 0
+            or (dev is not None and t.device != dev) or (shape is not None and tuple(t.shape) != tuple(shape))):
+        got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+        raise PcrlError(f"{what} must be a contiguous non-empty uint8 [X, Y, Z] bitmask on the GPU" + (f" of shape {tuple(shape)}" if shape else "")
+                        + f", got {got}")
+
+
+def _surf_spacing(spacing, what):
+    try:
+        sp = tuple(float(s) for s in spacing)
+    except (TypeError, ValueError):
+        sp = ()
+    if len(sp) != 3 or not all(s > 0 and s != float("inf") for s in sp):
+        raise PcrlError(f"{what}: the spacing must be three positive finite numbers, got {spacing!r}")
+    return sp
+
+
+def surf_extract(pred, gt, K, counts=None):
+    """The 6-connected surfaces of all K classes of a predicted and a ground-truth bitmask, uint8 [X, Y, Z] on the device (pcrl_surf_extract): a
+    voxel whose ground-truth byte has bit 7 set belongs to neither mask.  counts: int64 [K, 3], {TP, |pred|, |gt|} are ADDED (None: a zeroed row).
+    -> (surf_pred uint8 [X, Y, Z], surf_gt uint8 [X, Y, Z], counts)"""
+    _surf_mask(pred, "surf_extract: pred")
+    _surf_mask(gt, "surf_extract: gt", pred.device, pred.shape)
+    K = int(K)
+    if not 1 <= K <= 7:
+        raise PcrlError(f"surf_extract: 1 <= K <= 7 classes (bit 7 of a label byte means 'not counted'), got {K}")
+    if counts is None:
+        counts = torch.zeros((K, 3), dtype=torch.int64, device=pred.device)
+    elif counts.dtype != torch.int64 or tuple(counts.shape) != (K, 3) or not counts.is_contiguous() or counts.device != pred.device:
+        raise PcrlError(f"surf_extract: counts must be a contiguous int64 [{K}, 3] tensor on {pred.device}, got {counts.dtype} {tuple(counts.shape)}")
+    sp, sg = torch.empty_like(pred), torch.empty_like(gt)
+    lib().call("pcrl_surf_extract", pred, gt, sp, sg, counts, *pred.shape, K, stream_handle())
+    return sp, sg, counts
+
+
+def edt_max_axis():
+    """The longest axis pcrl_edt_sq takes (a whole line is staged in LDS)."""
+    return int(lib().call("pcrl_edt_max_axis"))
+
+
+def edt_sq(surf, bit, spacing=(1.0, 1.0, 1.0), out=None, steps=None):
+    """The exact squared Euclidean distance, float64 [X, Y, Z], of every voxel to the nearest voxel of `surf` (uint8 [X, Y, Z] on the device) that has
+    bit `bit` set, with the voxel spacing (sx, sy, sz) (pcrl_edt_sq); +inf everywhere when there is none.  steps: int64 [1], the scan steps executed
+    are ADDED (benchmarks)."""
+    _surf_mask(surf, "edt_sq: surf")
+    sp = _surf_spacing(spacing, "edt_sq")
+    bit = int(bit)
+    if not 0 <= bit <= 6:
+        raise PcrlError(f"edt_sq: bit {bit} outside 0..6")
+    X, Y, Z = surf.shape
+    top = edt_max_axis()
+    if max(X, Y, Z) > top:
+        raise PcrlError(f"edt_sq: volume {X} x {Y} x {Z}: an axis may have at most {top} voxels")
+    if out is None:
+        out = torch.empty((X, Y, Z), dtype=torch.float64, device=surf.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (X, Y, Z) or not out.is_contiguous() or out.device != surf.device:
+        raise PcrlError(f"edt_sq: out must be a contiguous float64 {(X, Y, Z)} tensor on {surf.device}, got {out.dtype} {tuple(out.shape)}")
+    if steps is not None and (steps.dtype != torch.int64 or steps.numel() != 1 or steps.device != surf.device):
+        raise PcrlError(f"edt_sq: steps must be an int64 [1] tensor on {surf.device}")
+    nb = lib().call("pcrl_edt_sq_ws_bytes", X, Y, Z)
+    ws = workspace(nb, surf.device) if nb else None
+    lib().call("pcrl_edt_sq", surf, bit, out, *sp, steps, ws, nb, X, Y, Z, stream_handle())
+    return out
+
+
+def surf_dist_stats(d2_to_gt, surf_pred, d2_to_pred, surf_gt, bit, q=0.95, record=None):
+    """One class's distance statistics (pcrl_surf_dist_stats): A = d2_to_gt on the prediction's surface, B = d2_to_pred on the ground truth's.
+    record: int64 [8] on the device (None: zeroed) -- n_a, n_b, lo, then float64 bit patterns: the exact order statistics of d2 over A u B at ranks
+    lo = floor(q (n - 1)), min(lo + 1, n - 1), n - 1, and the sums of sqrt(d2) over A and B; only the counts when a surface is empty.  -> record"""
+    _surf_mask(surf_pred, "surf_dist_stats: surf_pred")
+    dev, shape = surf_pred.device, tuple(surf_pred.shape)
+    _surf_mask(surf_gt, "surf_dist_stats: surf_gt", dev, shape)
+    for name, d in (("d2_to_gt", d2_to_gt), ("d2_to_pred", d2_to_pred)):
+        if not torch.is_tensor(d) or d.dtype != torch.float64 or tuple(d.shape) != shape or not d.is_contiguous() or d.device != dev:
+            raise PcrlError(f"surf_dist_stats: {name} must be a contiguous float64 {shape} tensor on {dev}")
+    bit, q = int(bit), float(q)
+    if not 0 <= bit <= 6:
+        raise PcrlError(f"surf_dist_stats: bit {bit} outside 0..6")
+    if not 0.0 <= q <= 1.0:
+        raise PcrlError(f"surf_dist_stats: the quantile {q} is outside [0, 1]")
+    if record is None:
+        record = torch.zeros(SURF_REC, dtype=torch.int64, device=dev)
+    elif record.dtype != torch.int64 or record.numel() != SURF_REC or not record.is_contiguous() or record.device != dev:
+        raise PcrlError(f"surf_dist_stats: record must be a contiguous int64 [{SURF_REC}] tensor on {dev}, got {record.dtype} {tuple(record.shape)}")
+    V = surf_pred.numel()
+    nb = lib().call("pcrl_surf_dist_stats_ws_bytes", V)
+    lib().call("pcrl_surf_dist_stats", d2_to_gt, surf_pred, d2_to_pred, surf_gt, bit, q, record, workspace(nb, dev), nb, V, stream_handle())
+    return record

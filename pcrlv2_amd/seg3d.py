@@ -3,12 +3,15 @@
     python seg3d.py train   --data DIR --phase finetune --weights PRETRAIN.pt --n_class 3 --in_channels 4 --save_best --output OUT
     python seg3d.py predict --data DIR --list test.txt --weights OUT/pcrlv2_seg3d_finetune_1.0_best.pt --out PRED
     python seg3d.py predict --data DIR --list test.txt --weights OUT/pcrlv2_seg3d_finetune_1.0_best.pt --out PRED --overlap 0.5 --window gaussian --probs
+    python seg3d.py score   --data DIR --list test.txt --pred PRED --n_class 3 --spacing 1,1,1 --csv scores.csv
 
 DIR holds <case>_img.npy [C,X,Y,Z] float32 / float16, <case>_seg.npy [X,Y,Z] uint8 (bit k = class k, bit 7 = not counted) and train.txt / val.txt /
 test.txt (pcrlv2_amd/data_seg.py); `--data synthetic` trains on phantoms.  The loop is pcrlv2_amd/train_seg.py, the model models.Segmenter3d, the
 output head and its Dice/BCE loss one HIP operator (csrc/seg_head.hip).  DESIGN.md section 15.  `--overlap F` (predict) and `--val_overlap F` (train)
 replace the stride-tiled patches by overlapping windows blended with a centre-weighted window (csrc/seg_blend.hip); 0, the
-default, is the tiled path.
+default, is the tiled path.  `score` compares the stored <case>_pred.npy of PRED with <case>_seg.npy: Dice, HD95, HD and ASSD per case and class, the
+distances in the units of --spacing (or of <case>_spacing.npy, three float64, where DIR has one), computed on the device (csrc/surface_dist.hip,
+DESIGN.md section 17).
 """
 from __future__ import annotations
 
@@ -60,6 +63,12 @@ def predict(args):
     return run(args)
 
 
+def score(args):
+    """Every refusal (spacing, --n_class, a missing or mis-shaped prediction) exits with its message in train_seg.score_plan, before anything touches a GPU."""
+    from .train_seg import score as run
+    return run(args)
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description="3D segmentation fine-tuning of the PCRLv2 network (HIP kernels on MI355X)")
     sub = ap.add_subparsers(dest="command", required=True)
@@ -101,12 +110,20 @@ def build_parser():
                     "stride-tiled patches, every voxel from one patch")
     pr.add_argument("--window", default="gaussian", help="blending window with --overlap > 0: gaussian | constant")
     pr.add_argument("--probs", action="store_true", help="with --overlap > 0: also write <case>_prob.npy, float16 [K, X, Y, Z]")
+    sc = sub.add_parser("score", help="Dice, HD95, HD and ASSD of stored <case>_pred.npy against <case>_seg.npy")
+    sc.add_argument("--data", required=True, help="directory with <case>_seg.npy (and, optionally, <case>_spacing.npy: three float64)")
+    sc.add_argument("--list", required=True, help="file of case names (in --data, or a path)")
+    sc.add_argument("--pred", required=True, help="directory with <case>_pred.npy (the --out of `predict`)")
+    sc.add_argument("--n_class", type=int, default=3, help="classes = bits of the label byte, 1..7")
+    sc.add_argument("--spacing", default="1,1,1", help="voxel size sx,sy,sz; a case's <case>_spacing.npy replaces it")
+    sc.add_argument("--csv", default="", help="also write case,class,dice,hd95,hd,assd,n_pred,n_gt to this file")
+    sc.add_argument("--gpu", type=int, default=0)
     return ap
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    return {"train": train, "predict": predict}[args.command](args)
+    return {"train": train, "predict": predict, "score": score}[args.command](args)
 
 
 if __name__ == "__main__":

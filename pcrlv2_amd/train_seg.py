@@ -11,6 +11,9 @@ logits kept per case, one blend kernel); at 0, the default
 The run, the epoch and the bracket around a step are pcrlv2_amd.loop's; validation is ONE pass of Segmenter3d.infer over the tiles with the integer
 counts {TP, |pred|, |gt|} per (case, class) and the loss sums kept on the device, one all_reduce of both when there is a process group (cases are
 sharded by rank, every rank indexes the global case table) and one host read-back.
+
+`seg3d.py score` (surface_metrics, score) scores stored masks: Dice, HD95, HD and ASSD per case and class, the surfaces, the exact
+distance transforms and the order statistics on the device (csrc/surface_dist.hip), one host read-back per case.
 """
 from __future__ import print_function
 
@@ -259,3 +262,150 @@ def predict(args, log=print):
             np.save(os.path.join(args.out, name + "_pred.npy"), predict_case(model, case, crop, args.b))
     log(f"[seg3d] {len(names)} masks written to {args.out}")
     return len(names)
+
+
+# ---- score: surface distances of stored masks -----------------------------------------------------------------
+SURFACE_KEYS = ("hd95", "hd", "assd")
+
+
+def _lerp(a, b, t):
+    """numpy's linear interpolation between two neighbouring order statistics (numpy.lib._function_base_impl._lerp), one float64 operation at a time."""
+    d = b - a
+    return b - d * (1.0 - t) if t >= 0.5 else a + d * t
+
+
+def surface_from_records(records, q=0.95):
+    """Host, float64: the records of ops.surf_dist_stats, int64 [K][8] -> {'hd95', 'hd', 'assd': float64 [K], 'n_pred', 'n_gt': int64 [K]}.
+    hd95 is numpy.percentile(U, 100 q) with the default linear method on the distances U = sqrt(d2) (sqrt is monotone, so the order statistics of
+    the distances are the square roots of those of d2); hd = max U; assd = (mean A + mean B) / 2, MedPy's.  Both surfaces empty: all three are 0.0;
+    exactly one empty: all three are NaN."""
+    rec = np.ascontiguousarray(np.asarray(records, dtype=np.int64).reshape(-1, _ops.SURF_REC))
+    as_f = rec.view(np.float64)
+    K = rec.shape[0]
+    out = {k: np.zeros(K, dtype=np.float64) for k in SURFACE_KEYS}
+    out["n_pred"], out["n_gt"] = rec[:, 0].copy(), rec[:, 1].copy()
+    for k in range(K):
+        na, nb = int(rec[k, 0]), int(rec[k, 1])
+        if na == 0 and nb == 0:
+            continue
+        if na == 0 or nb == 0:
+            for key in SURFACE_KEYS:
+                out[key][k] = np.nan
+            continue
+        n = na + nb
+        virtual = np.float64(q) * np.float64(n - 1)
+        lo = np.floor(virtual)
+        d_lo, d_hi, d_max = (np.sqrt(as_f[k, 3 + i]) for i in range(3))
+        out["hd95"][k] = d_lo if virtual >= n - 1 else _lerp(d_lo, d_hi, virtual - lo)
+        out["hd"][k] = d_max
+        out["assd"][k] = (as_f[k, 6] / na + as_f[k, 7] / nb) / 2.0
+    return out
+
+
+def surface_metrics(pred, gt, K, spacing=(1.0, 1.0, 1.0), q=0.95):
+    """HD95, HD and ASSD per class of a predicted against a ground-truth bitmask, device uint8 tensors [X, Y, Z] (bit k = class k; a voxel with bit 7
+    of `gt` set belongs to neither mask): the surfaces of all classes in one launch, then per class the two exact squared distance transforms with
+    the voxel `spacing` and the order statistics into ONE device table [K][8]; ONE host read-back; the rest (sqrt, numpy's interpolation, the
+    empty-mask conventions) on the host in float64.
+    -> {'hd95', 'hd', 'assd': float64 [K], 'n_pred', 'n_gt': int64 [K] surface voxels, 'counts': int64 [K, 3] = {TP, |pred|, |gt|}}"""
+    K = int(K)
+    sp, sg, counts = _ops.surf_extract(pred, gt, K)
+    table = torch.zeros((K, _ops.SURF_REC), dtype=torch.int64, device=pred.device)
+    d2g = torch.empty(tuple(pred.shape), dtype=torch.float64, device=pred.device)
+    d2p = torch.empty_like(d2g)
+    for k in range(K):
+        _ops.edt_sq(sg, k, spacing, out=d2g)
+        _ops.edt_sq(sp, k, spacing, out=d2p)
+        _ops.surf_dist_stats(d2g, sp, d2p, sg, k, q, record=table[k])
+    host = torch.cat([table.reshape(-1), counts.reshape(-1)]).cpu().numpy()
+    out = surface_from_records(host[:K * _ops.SURF_REC], q)
+    out["counts"] = host[K * _ops.SURF_REC:].reshape(K, 3).copy()
+    return out
+
+
+def crop_to_masks(pred, seg):
+    """Both arrays cut to the bounding box of (pred | seg) & 0x7f, or None when that is empty.  Exact for the surface metrics: both masks are empty
+    outside the box, and a face of the box behaves like a face of the volume (what lies beyond is not in the mask)."""
+    any_bit = ((pred | seg) & 0x7F) != 0
+    if not any_bit.any():
+        return None
+    box = []
+    for axis in range(3):
+        hit = np.nonzero(any_bit.any(axis=tuple(a for a in range(3) if a != axis)))[0]
+        box.append(slice(int(hit[0]), int(hit[-1]) + 1))
+    box = tuple(box)
+    return np.ascontiguousarray(pred[box]), np.ascontiguousarray(seg[box])
+
+
+def parse_spacing(spacing, what="--spacing"):
+    """'sx,sy,sz' or a sequence -> three positive finite floats, else SystemExit."""
+    try:
+        sp = tuple(float(v) for v in (spacing.split(",") if isinstance(spacing, str) else np.asarray(spacing).reshape(-1).tolist()))
+    except (TypeError, ValueError):
+        sp = ()
+    if len(sp) != 3 or not all(np.isfinite(v) and v > 0 for v in sp):
+        raise SystemExit(f"{what} {spacing}: three positive finite numbers sx,sy,sz (the voxel size along X, Y, Z)")
+    return sp
+
+
+def score_plan(args):
+    """Everything `score` refuses, checked on the host before a GPU is touched.  -> [(case, seg path, pred path, spacing)]"""
+    K = _data.check_n_class(args.n_class)
+    default = parse_spacing(args.spacing)
+    plan = []
+    for name in _data.read_list(args.data, args.list):
+        seg_path, pred_path = os.path.join(args.data, name + "_seg.npy"), os.path.join(args.pred, name + "_pred.npy")
+        sp_path = os.path.join(args.data, name + "_spacing.npy")
+        if not os.path.exists(seg_path):
+            raise SystemExit(f"{seg_path}: missing (the ground truth of a case is <case>_seg.npy [X,Y,Z] uint8)")
+        if not os.path.exists(pred_path):
+            raise SystemExit(f"{pred_path}: missing (the prediction of a case is <case>_pred.npy, as `seg3d.py predict` writes it)")
+        seg, pred = np.load(seg_path, mmap_mode="r"), np.load(pred_path, mmap_mode="r")
+        if seg.ndim != 3 or seg.dtype != np.uint8:
+            raise SystemExit(f"{seg_path}: expected a uint8 array [X, Y, Z], got {seg.dtype} {seg.shape}")
+        if pred.dtype != np.uint8 or pred.shape != seg.shape:
+            raise SystemExit(f"{pred_path}: a prediction is a uint8 array of its label's shape {seg.shape}, got {pred.dtype} {pred.shape}")
+        spacing = parse_spacing(np.load(sp_path), sp_path + ":") if os.path.exists(sp_path) else default
+        plan.append((name, seg_path, pred_path, spacing))
+    if not plan:
+        raise SystemExit(f"{args.list}: no cases")
+    return K, plan
+
+
+def score(args, log=print):
+    """`seg3d.py score`: Dice, HD95, HD and ASSD per case and class of stored predictions.  -> the rows (case, class, dice, hd95, hd, assd, n_pred, n_gt)"""
+    K, plan = score_plan(args)
+    device = None
+    rows = []
+    for name, seg_path, pred_path, spacing in plan:
+        cut = crop_to_masks(np.load(pred_path), np.load(seg_path))
+        if cut is None:          # nothing predicted, nothing labelled: every class scores Dice 1 and distance 0 without a launch
+            m = {key: np.zeros(K) for key in SURFACE_KEYS}
+            m.update(n_pred=np.zeros(K, dtype=np.int64), n_gt=np.zeros(K, dtype=np.int64), counts=np.zeros((K, 3), dtype=np.int64))
+        else:
+            if device is None:
+                device = torch.device("cuda", args.gpu)
+                torch.cuda.set_device(device)
+            top = _ops.edt_max_axis()
+            if max(cut[0].shape) > top:
+                raise SystemExit(f"{name}: the bounding box of its masks is {cut[0].shape}; an axis may have at most {top} voxels")
+            m = surface_metrics(torch.from_numpy(cut[0]).to(device), torch.from_numpy(cut[1]).to(device), K, spacing)
+        for k in range(K):
+            dice = dice_from_counts([[m["counts"][k].tolist()]])[1]
+            rows.append((name, k, dice, float(m["hd95"][k]), float(m["hd"][k]), float(m["assd"][k]), int(m["n_pred"][k]), int(m["n_gt"][k])))
+        log("{0}\tspacing {1}\t".format(name, ",".join("%g" % s for s in spacing)) + "\t".join(
+            "class {0}: Dice {1:.4f} HD95 {2:.3f} HD {3:.3f} ASSD {4:.3f}".format(*r[1:6]) for r in rows[-K:]))
+    means = []
+    for k in range(K):
+        part = ["class %d:" % k]
+        for col, label in ((2, "Dice"), (3, "HD95"), (4, "HD"), (5, "ASSD")):
+            vals = [r[col] for r in rows if r[1] == k and r[col] == r[col]]      # a NaN (one empty surface) is left out of the mean
+            part.append("{0} {1:.4f} ({2})".format(label, sum(vals) / len(vals) if vals else float("nan"), len(vals)))
+        means.append(" ".join(part))
+    log("Score: {0} cases\t".format(len(plan)) + "\t".join(means))
+    if args.csv:
+        with open(args.csv, "w") as f:
+            f.write("case,class,dice,hd95,hd,assd,n_pred,n_gt\n")
+            for r in rows:
+                f.write("{0},{1},{2!r},{3!r},{4!r},{5!r},{6},{7}\n".format(*r))
+    return rows
