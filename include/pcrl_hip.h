@@ -839,6 +839,36 @@ size_t pcrl_surf_dist_stats_ws_bytes(int64_t V);
 int pcrl_surf_dist_stats(const double* d2_to_gt, const uint8_t* surf_pred, const double* d2_to_pred, const uint8_t* surf_gt, int bit, double q,
                          int64_t* record, void* ws, size_t ws_bytes, int64_t V, pcrl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * 3D path, connected components of a segmentation mask and the clean-up rules on them (csrc/components.hip; integer only).
+ *   Masks are the uint8 bitmasks of the segmenter, [X][Y][Z], Z contiguous: bit k = class k.  A class-k voxel is one whose byte has bit k set; every
+ *   other bit is ignored by the labelling and copied by the filter.  Limits: 1 <= X * Y * Z < 2^31 (voxel indices are 32-bit), any other shape,
+ *   axes of length 1 and shapes that are no multiple of the tile included; bit in 0..6; PCRL_EINVAL otherwise, before any launch.
+ * pcrl_ccl_label -- the components of class `bit` under connectivity 6, 18 or 26 (faces; faces and edges; faces, edges and corners:
+ *   scipy.ndimage.generate_binary_structure(3, 1 | 2 | 3)).
+ *       labels int32 [X][Y][Z]   0 for background, otherwise the component's number 1..n
+ *       sizes  int32 [>= (X * Y * Z + 1) / 2]   sizes[c - 1] = the voxels of component c; only [0, n) is written (no connectivity has more
+ *              than ceil(V / 2) components)
+ *       n      int32 [1]   the number of components, on the device
+ *   Numbering: components are numbered by the ascending linear index ((x * Y + y) * Z + z) of their first voxel -- scipy.ndimage.label's numbering,
+ *   so labels equals its result without any canonicalisation.  Integer atomics only, and every output is independent of their order: two runs give
+ *   identical bytes.  ws: pcrl_ccl_ws_bytes(X, Y, Z) bytes, 4-byte aligned (0 for a shape that is refused).
+ *   pcrl_ccl_tile: the tile (voxels along X, Y, Z) one block resolves in LDS before tiles are merged.  Both queries are host functions.
+ * pcrl_ccl_filter -- out = mask with bit `bit` cleared at every voxel whose component (labels, sizes, n of that bit, as pcrl_ccl_label wrote them)
+ *   fails the rule; all other bits, and every voxel with label 0, are copied.
+ *       keep_largest != 0   only the component with the most voxels survives; among equals the lowest label (selected on the device by one
+ *                           block over sizes[0, n), keys (size << 32) | ~label)
+ *       min_voxels > 0      only components of at least min_voxels voxels survive
+ *   Both: a component must pass both.  Neither: a copy.  n == 0 (an empty class): a copy.  out must not be mask; min_voxels >= 0.
+ *   ws: pcrl_ccl_filter_ws_bytes() bytes, 4-byte aligned. */
+int pcrl_ccl_tile(int* tx, int* ty, int* tz);
+size_t pcrl_ccl_ws_bytes(int X, int Y, int Z);
+int pcrl_ccl_label(const uint8_t* mask, int bit, int connectivity, int* labels, int* sizes, int* n, void* ws, size_t ws_bytes, int X, int Y, int Z,
+                   pcrl_stream_t stream);
+size_t pcrl_ccl_filter_ws_bytes(void);
+int pcrl_ccl_filter(const uint8_t* mask, const int* labels, const int* sizes, const int* n, uint8_t* out, int bit, int keep_largest,
+                    int64_t min_voxels, void* ws, size_t ws_bytes, int X, int Y, int Z, pcrl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1887,3 +1887,69 @@ def surf_dist_stats(d2_to_gt, surf_pred, d2_to_pred, surf_gt, bit, q=0.95, recor
     nb = lib().call("pcrl_surf_dist_stats_ws_bytes", V)
     lib().call("pcrl_surf_dist_stats", d2_to_gt, surf_pred, d2_to_pred, surf_gt, bit, q, record, workspace(nb, dev), nb, V, stream_handle())
     return record
+
+
+# ----------------------------------------------------------------------------------------------
+# connected components of a mask's class and the clean-up rules on them (csrc/components.hip)
+# ----------------------------------------------------------------------------------------------
+CCL_CONNECTIVITIES = (6, 18, 26)
+
+
+def ccl_tile():
+    """The tile (voxels along X, Y, Z) that one block of pcrl_ccl_label resolves in LDS.  A host function: no GPU is touched."""
+    import ctypes
+    t = (ctypes.c_int * 3)()
+    base = ctypes.addressof(t)
+    lib().call("pcrl_ccl_tile", base, base + 4, base + 8)
+    return tuple(int(v) for v in t)
+
+
+def _ccl_bit(bit, what):
+    bit = int(bit)
+    if not 0 <= bit <= 6:
+        raise PcrlError(f"{what}: bit {bit} outside 0..6")
+    return bit
+
+
+def label_components(mask, bit, connectivity=6):
+    """The connected components of class `bit` of a uint8 [X, Y, Z] bitmask on the device under connectivity 6, 18 or 26 (pcrl_ccl_label), numbered
+    1..n by the ascending linear index of their first voxel: scipy.ndimage.label's numbering.  ONE host read-back, of n.
+    -> (labels int32 [X, Y, Z], 0 = background; sizes int32 [n], sizes[c - 1] = the voxels of component c)"""
+    if connectivity not in CCL_CONNECTIVITIES:
+        raise PcrlError(f"label_components: connectivity {connectivity!r} is not 6, 18 or 26")
+    bit = _ccl_bit(bit, "label_components")
+    _surf_mask(mask, "label_components: mask")
+    X, Y, Z = mask.shape
+    V = X * Y * Z
+    if V >= 1 << 31:
+        raise PcrlError(f"label_components: volume {X} x {Y} x {Z} has 2^31 voxels or more (voxel indices are 32-bit)")
+    dev = mask.device
+    labels = torch.empty((X, Y, Z), dtype=torch.int32, device=dev)
+    sizes = torch.empty((V + 1) // 2, dtype=torch.int32, device=dev)
+    n = torch.empty(1, dtype=torch.int32, device=dev)
+    nb = lib().call("pcrl_ccl_ws_bytes", X, Y, Z)
+    lib().call("pcrl_ccl_label", mask, bit, int(connectivity), labels, sizes, n, workspace(nb, dev), nb, X, Y, Z, stream_handle())
+    return labels, sizes[:int(n)]
+
+
+def filter_components(mask, labels, sizes, bit, keep_largest=False, min_voxels=0):
+    """`mask` with bit `bit` cleared at every voxel whose component fails the rule (pcrl_ccl_filter); labels, sizes: label_components' of that bit.
+    keep_largest: only the component with the most voxels survives (among equals the lowest label); min_voxels: only components of at least that
+    many voxels survive; both: a component must pass both.  Every other bit is copied.  No host read-back.  -> a new uint8 [X, Y, Z] mask"""
+    bit = _ccl_bit(bit, "filter_components")
+    _surf_mask(mask, "filter_components: mask")
+    dev, shape = mask.device, tuple(mask.shape)
+    if not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != shape or not labels.is_contiguous() or labels.device != dev:
+        raise PcrlError(f"filter_components: labels must be a contiguous int32 {shape} tensor on {dev}")
+    if not torch.is_tensor(sizes) or sizes.dtype != torch.int32 or sizes.dim() != 1 or not sizes.is_contiguous() or sizes.device != dev:
+        raise PcrlError(f"filter_components: sizes must be a contiguous int32 [n] tensor on {dev}")
+    min_voxels = int(min_voxels)
+    if min_voxels < 0:
+        raise PcrlError(f"filter_components: min_voxels {min_voxels} is negative")
+    n = torch.full((1,), sizes.numel(), dtype=torch.int32, device=dev)
+    out = torch.empty_like(mask)
+    nb = lib().call("pcrl_ccl_filter_ws_bytes")
+    if sizes.numel() == 0:
+        sizes = n          # an empty class: torch gives an empty view no address; with n == 0 the kernels read no size
+    lib().call("pcrl_ccl_filter", mask, labels, sizes, n, out, bit, 1 if keep_largest else 0, min_voxels, workspace(nb, dev), nb, *shape, stream_handle())
+    return out

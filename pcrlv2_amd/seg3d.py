@@ -3,6 +3,8 @@
     python seg3d.py train   --data DIR --phase finetune --weights PRETRAIN.pt --n_class 3 --in_channels 4 --save_best --output OUT
     python seg3d.py predict --data DIR --list test.txt --weights OUT/pcrlv2_seg3d_finetune_1.0_best.pt --out PRED
     python seg3d.py predict --data DIR --list test.txt --weights OUT/pcrlv2_seg3d_finetune_1.0_best.pt --out PRED --overlap 0.5 --window gaussian --probs
+    python seg3d.py predict --data DIR --list test.txt --weights OUT/pcrlv2_seg3d_finetune_1.0_best.pt --out PRED --keep_largest all --min_voxels 8
+    python seg3d.py postprocess --pred PRED --list DIR/test.txt --out CLEAN --n_class 3 --keep_largest 0,2 --min_voxels 8 --connectivity 26
     python seg3d.py score   --data DIR --list test.txt --pred PRED --n_class 3 --spacing 1,1,1 --csv scores.csv
 
 DIR holds <case>_img.npy [C,X,Y,Z] float32 / float16, <case>_seg.npy [X,Y,Z] uint8 (bit k = class k, bit 7 = not counted) and train.txt / val.txt /
@@ -11,7 +13,10 @@ output head and its Dice/BCE loss one HIP operator (csrc/seg_head.hip).  DESIGN.
 replace the stride-tiled patches by overlapping windows blended with a centre-weighted window (csrc/seg_blend.hip); 0, the
 default, is the tiled path.  `score` compares the stored <case>_pred.npy of PRED with <case>_seg.npy: Dice, HD95, HD and ASSD per case and class, the
 distances in the units of --spacing (or of <case>_spacing.npy, three float64, where DIR has one), computed on the device (csrc/surface_dist.hip,
-DESIGN.md section 17).
+DESIGN.md section 17).  `postprocess` cleans stored predictions by their connected components (6, 18 or 26 neighbours) into another directory that
+`score --pred` reads unchanged: the classes of --keep_largest keep only their largest component, and with --min_voxels N every class loses its
+components below N voxels; `predict` takes the same three options and cleans a mask on the device before it is written (csrc/components.hip,
+DESIGN.md section 18).  Without them `predict` writes what it always wrote.
 """
 from __future__ import annotations
 
@@ -69,6 +74,19 @@ def score(args):
     return run(args)
 
 
+def postprocess(args):
+    """Every refusal (no rule, a class outside --n_class, a negative volume, the connectivity, a missing or mis-typed prediction, --out equal to --pred)
+    exits with its message in train_seg.postprocess_plan, before anything touches a GPU."""
+    from .train_seg import postprocess as run
+    return run(args)
+
+
+def _cleanup_options(p):
+    p.add_argument("--keep_largest", default="", help="classes that keep only their largest connected component: 0,2 or `all`")
+    p.add_argument("--min_voxels", type=int, default=0, help="every class loses its connected components of fewer voxels; 0 = off")
+    p.add_argument("--connectivity", type=int, default=6, help="neighbours of a voxel: 6 (faces), 18 (and edges) or 26 (and corners)")
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description="3D segmentation fine-tuning of the PCRLv2 network (HIP kernels on MI355X)")
     sub = ap.add_subparsers(dest="command", required=True)
@@ -110,6 +128,14 @@ def build_parser():
                     "stride-tiled patches, every voxel from one patch")
     pr.add_argument("--window", default="gaussian", help="blending window with --overlap > 0: gaussian | constant")
     pr.add_argument("--probs", action="store_true", help="with --overlap > 0: also write <case>_prob.npy, float16 [K, X, Y, Z]")
+    _cleanup_options(pr)
+    pp = sub.add_parser("postprocess", help="connected-component clean-up of stored <case>_pred.npy into another directory")
+    pp.add_argument("--pred", required=True, help="directory with <case>_pred.npy (the --out of `predict`)")
+    pp.add_argument("--list", required=True, help="file of case names (in --pred, or a path)")
+    pp.add_argument("--out", required=True, help="output directory for the cleaned <case>_pred.npy; not --pred")
+    pp.add_argument("--n_class", type=int, default=3, help="classes = bits of the mask byte, 1..7")
+    _cleanup_options(pp)
+    pp.add_argument("--gpu", type=int, default=0)
     sc = sub.add_parser("score", help="Dice, HD95, HD and ASSD of stored <case>_pred.npy against <case>_seg.npy")
     sc.add_argument("--data", required=True, help="directory with <case>_seg.npy (and, optionally, <case>_spacing.npy: three float64)")
     sc.add_argument("--list", required=True, help="file of case names (in --data, or a path)")
@@ -123,7 +149,7 @@ def build_parser():
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    return {"train": train, "predict": predict, "score": score}[args.command](args)
+    return {"train": train, "predict": predict, "score": score, "postprocess": postprocess}[args.command](args)
 
 
 if __name__ == "__main__":

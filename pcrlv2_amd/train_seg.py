@@ -14,6 +14,9 @@ sharded by rank, every rank indexes the global case table) and one host read-bac
 
 `seg3d.py score` (surface_metrics, score) scores stored masks: Dice, HD95, HD and ASSD per case and class, the surfaces, the exact
 distance transforms and the order statistics on the device (csrc/surface_dist.hip), one host read-back per case.
+
+`seg3d.py postprocess` and the clean-up options of `predict` (postprocess_mask, postprocess) drop connected components of a mask's
+classes on the device (csrc/components.hip): all but the largest, and / or those below a volume.
 """
 from __future__ import print_function
 
@@ -245,9 +248,12 @@ def predict_case(model, case, crop, b):
 def predict(args, log=print):
     crop = _data.parse_crop(args.crop)
     overlap, window, want_probs = float(getattr(args, "overlap", 0.0)), getattr(args, "window", "gaussian"), bool(getattr(args, "probs", False))
+    rules = parse_cleanup(args)          # None (the default): the masks are written as predicted
     device = torch.device("cuda", args.gpu)
     torch.cuda.set_device(device)
     model = load_segmenter(args.weights, device, args.amp)
+    if rules is not None:
+        rules = (resolve_keep(rules[0], model.n_class),) + rules[1:]
     os.makedirs(args.out, exist_ok=True)
     names = _data.read_list(args.data, args.list)
     for name in names:
@@ -255,13 +261,124 @@ def predict(args, log=print):
         case.seg = None          # the prediction does not look at labels
         if overlap > 0:
             mask, probs, _ = sliding_window(model, case, crop, args.b, overlap, window, want_probs=want_probs)
+            if rules is not None:
+                mask = postprocess_mask(mask, model.n_class, *rules)[0]
             np.save(os.path.join(args.out, name + "_pred.npy"), mask.cpu().numpy())
             if want_probs:
                 np.save(os.path.join(args.out, name + "_prob.npy"), probs.half().cpu().numpy())
         else:
-            np.save(os.path.join(args.out, name + "_pred.npy"), predict_case(model, case, crop, args.b))
+            mask = predict_case(model, case, crop, args.b)
+            if rules is not None:         # the stitched mask is on the host: one upload
+                mask = postprocess_mask(torch.from_numpy(mask).to(device), model.n_class, *rules)[0].cpu().numpy()
+            np.save(os.path.join(args.out, name + "_pred.npy"), mask)
     log(f"[seg3d] {len(names)} masks written to {args.out}")
     return len(names)
+
+
+# ---- postprocess: connected-component clean-up of masks -----------------------------------------------------------
+def kept_components(sizes, keep_largest, min_voxels):
+    """Host: the rule of ops.filter_components on the sizes of one class's components -> bool [n].  keep_largest: the first maximum (the lowest label
+    among equals); min_voxels: sizes >= min_voxels; both: both."""
+    sizes = np.asarray(sizes, dtype=np.int64)
+    keep = np.ones(len(sizes), dtype=bool)
+    if keep_largest and len(sizes):
+        keep = np.arange(len(sizes)) == int(np.argmax(sizes))
+    if min_voxels > 0:
+        keep &= sizes >= min_voxels
+    return keep
+
+
+def postprocess_mask(mask, K, keep_largest=(), min_voxels=0, connectivity=6):
+    """Connected-component clean-up of a device uint8 [X, Y, Z] bitmask, class by class (the classes are independent bits, so their order does not
+    matter): the classes in `keep_largest` keep only their largest component (among equals the one that comes first in C order), and with
+    min_voxels > 0 every class loses its components below that volume; components under connectivity 6, 18 or 26.  A class that no rule touches is
+    not labelled.  Per class that is: one read-back of the component count and one of the sizes, for the report.
+    -> (mask, report): report[k] = {'before', 'after': components (None: class k was not touched), 'removed': voxels}"""
+    K, keep, min_voxels = int(K), {int(k) for k in keep_largest}, int(min_voxels)
+    report = []
+    for k in range(K):
+        if k not in keep and min_voxels <= 0:
+            report.append({"before": None, "after": None, "removed": 0})
+            continue
+        labels, sizes = _ops.label_components(mask, k, connectivity)
+        mask = _ops.filter_components(mask, labels, sizes, k, k in keep, min_voxels)
+        host = sizes.cpu().numpy().astype(np.int64)
+        kept = kept_components(host, k in keep, min_voxels)
+        report.append({"before": len(host), "after": int(kept.sum()), "removed": int(host[~kept].sum())})
+    return mask, report
+
+
+def parse_cleanup(args):
+    """--keep_largest, --min_voxels and --connectivity of `predict` and `postprocess` (absent attributes: the defaults), checked on the host.
+    -> None when neither rule is given, else (keep, min_voxels, connectivity) with keep a tuple of classes or 'all' (resolve_keep)."""
+    raw = str(getattr(args, "keep_largest", "") or "").strip()
+    min_voxels, connectivity = getattr(args, "min_voxels", 0) or 0, getattr(args, "connectivity", 6)
+    if connectivity not in _ops.CCL_CONNECTIVITIES:
+        raise SystemExit(f"--connectivity {connectivity}: 6 (faces), 18 (faces and edges) or 26 (faces, edges and corners)")
+    if min_voxels < 0:
+        raise SystemExit(f"--min_voxels {min_voxels}: the smallest volume of a component that stays, in voxels; 0 or more")
+    keep = "all" if raw == "all" else ()
+    if raw and raw != "all":
+        try:
+            keep = tuple(sorted({int(v) for v in raw.split(",")}))
+        except ValueError:
+            keep = (-1,)
+        if min(keep) < 0:
+            raise SystemExit(f"--keep_largest {raw}: class numbers separated by commas, or `all`")
+    if not keep and min_voxels == 0:
+        return None
+    return keep, int(min_voxels), int(connectivity)
+
+
+def resolve_keep(keep, K):
+    """'all' -> every class; a class >= K is refused."""
+    if keep == "all":
+        return tuple(range(K))
+    for k in keep:
+        if k >= K:
+            raise SystemExit(f"--keep_largest {k}: the masks have the classes 0..{K - 1} (--n_class {K})")
+    return tuple(keep)
+
+
+def postprocess_plan(args):
+    """Everything `postprocess` refuses, checked on the host before a GPU is touched.  -> (K, (keep, min_voxels, connectivity), [(case, in, out)])"""
+    K = _data.check_n_class(args.n_class)
+    rules = parse_cleanup(args)
+    if rules is None:
+        raise SystemExit("postprocess: no rule given: --keep_largest CLASSES|all and / or --min_voxels N")
+    rules = (resolve_keep(rules[0], K),) + rules[1:]
+    if os.path.realpath(args.out) == os.path.realpath(args.pred):
+        raise SystemExit(f"--out {args.out}: the same directory as --pred; the cleaned masks would overwrite the predictions they were made from")
+    plan = []
+    for name in _data.read_list(args.pred, args.list):
+        path = os.path.join(args.pred, name + "_pred.npy")
+        if not os.path.exists(path):
+            raise SystemExit(f"{path}: missing (the prediction of a case is <case>_pred.npy, as `seg3d.py predict` writes it)")
+        pred = np.load(path, mmap_mode="r")
+        if pred.ndim != 3 or pred.dtype != np.uint8 or pred.size == 0 or pred.size >= 1 << 31:
+            raise SystemExit(f"{path}: a prediction is a non-empty uint8 array [X, Y, Z] of fewer than 2^31 voxels, got {pred.dtype} {pred.shape}")
+        plan.append((name, path, os.path.join(args.out, name + "_pred.npy")))
+    if not plan:
+        raise SystemExit(f"{args.list}: no cases")
+    return K, rules, plan
+
+
+def postprocess(args, log=print):
+    """`seg3d.py postprocess`: the stored predictions of --pred cleaned into --out.  -> [(case, report)]"""
+    K, rules, plan = postprocess_plan(args)
+    device = torch.device("cuda", args.gpu)
+    torch.cuda.set_device(device)
+    os.makedirs(args.out, exist_ok=True)
+    done = []
+    for name, src, dst in plan:
+        mask, report = postprocess_mask(torch.from_numpy(np.load(src)).to(device), K, *rules)
+        np.save(dst, mask.cpu().numpy())
+        done.append((name, report))
+        log(name + "\t" + "\t".join("class {0}: components {1} -> {2}, {3} voxels removed".format(k, r["before"], r["after"], r["removed"])
+                                    for k, r in enumerate(report) if r["before"] is not None))
+    log("Postprocess: {0} cases, connectivity {1}\t".format(len(plan), rules[2]) + "\t".join(
+        "class {0}: {1} voxels removed".format(k, sum(rep[k]["removed"] for _, rep in done)) for k in range(K)))
+    return done
 
 
 # ---- score: surface distances of stored masks (DESIGN.md section 17) -----------------------------------------------------------------
