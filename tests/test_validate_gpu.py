@@ -277,6 +277,11 @@ def test_val_metrics_kernel_against_float64_torch(B):
     ref = _metrics64(out1, masks, gt, f1, f2, fl, B)
     errs = _check_each(host[:10] / B, ref, f"val_metrics B={B}")
     print(f"val_metrics B={B}: max|d| per metric = " + " ".join(f"{e:.1e}" for e in errs))
+    # the kernel is float64 throughout: the relative bound test_validate2d_gpu.py asserts for its twin
+    got = host[:10] / B
+    rel = [abs(float(got[i] - ref[i])) / abs(float(ref[i])) for i in range(10)]
+    print(f"val_metrics B={B}: relative distance per metric = " + " ".join(f"{e:.1e}" for e in rel))
+    assert max(rel) <= 1e-12, rel
 
 
 # ---- 5. validate assembly, tight ------------------------------------------------------------------------------------------------------
