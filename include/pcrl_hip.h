@@ -869,6 +869,24 @@ size_t pcrl_ccl_filter_ws_bytes(void);
 int pcrl_ccl_filter(const uint8_t* mask, const int* labels, const int* sizes, const int* n, uint8_t* out, int bit, int keep_largest,
                     int64_t min_voxels, void* ws, size_t ws_bytes, int X, int Y, int Z, pcrl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * 3D path, joint image / label augmentation of segmentation training crops (csrc/seg_augment.hip).
+ * pcrl_seg_aug_resample -- ONE launch resamples a batch of source boxes into training crops, image channels and label bitmask through the same
+ *   geometry:  src [B][C][Sx][Sy][Sz] float32 (src_half = 0) or float16 (src_half = 1), src_lab uint8 [B][Sx][Sy][Sz]  ->
+ *   y float32 [B][C][X][Y][Z], lab uint8 [B][X][Y][Z];  inv float32 [B][12]: the rows (m0 m1 m2 t) of x, y and z;  gain, bias float32 [B][C].
+ *   For output voxel i = (ix, iy, iz), in float32:
+ *       c = i + 0.5 - (X, Y, Z) / 2          s = M c + t + (Sx, Sy, Sz) / 2 - 0.5      (flips are sign changes of M, folded in by the host)
+ *       y[b][ch][i] = gain[b][ch] * T + bias[b][ch],  T = the trilinear sample of channel ch at s, a corner outside the source box contributing 0
+ *                     (scipy.ndimage.affine_transform(order=1, mode='grid-constant', cval=0)); float16 sources are widened exactly
+ *       lab[b][i]   = src_lab[b][n], n = floor(s + 0.5) per axis (a tie goes up: s = -0.5 is voxel 0), 0x80 where n is outside the box
+ *                     (order=0, mode='grid-constant', cval=0x80): nearest neighbour, no byte that the source does not hold except 0x80
+ *   The coordinate, the corner offsets and the weights are formed once per voxel and shared by all channels and the label.  Every read is
+ *   bounds-checked in the kernel: no matrix, NaN included, reaches memory outside the box.  No atomics: two runs give identical bytes.
+ *   PCRL_EINVAL, before any launch: a null pointer; B outside 1..65535; C outside 1..16; an extent < 1; a source box or a crop of 2^31 voxels or
+ *   more; y or lab overlapping src, src_lab or each other. */
+int pcrl_seg_aug_resample(const void* src, int src_half, const uint8_t* src_lab, float* y, uint8_t* lab, const float* inv, const float* gain,
+                          const float* bias, int B, int C, int Sx, int Sy, int Sz, int X, int Y, int Z, pcrl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,9 +13,14 @@ forward has the training crop's shape.  No whole-volume forward.
 Overlap-blended sliding windows (window_axis, windows, blend_weights; the pass itself is train_seg.sliding_window): crop-sized patches at stride
 int(crop * (1 - overlap)), the last one of an axis shifted back inside the volume, every voxel's logits the window-weighted mean over the patches
 that cover it.  The tiled path above is what `--overlap 0` (the default) runs.
+
+Training-time augmentation (AugConfig, source_extent, cut_box, draw_aug_crop; CropLoader(aug=...)): the host draws rotation,
+zoom, flips and per-channel intensity parameters and cuts a source box around the crop; image channels and label bitmask are resampled together on
+the device (ops.seg_augment, csrc/seg_augment.hip) by train_seg.train_step.  Without `aug` nothing changes.
 """
 from __future__ import annotations
 
+import dataclasses
 import os
 
 import numpy as np
@@ -209,15 +214,217 @@ def draw_crop(rng, case, crop, centred):
     return np.ascontiguousarray(x), np.ascontiguousarray(lab), {"start": start, "flips": flips, "voxel": voxel}
 
 
+# ---- training-time augmentation: the host side of csrc/seg_augment.hip -----------------------------------------------
+MAX_ROTATE = 45.0
+
+
+@dataclasses.dataclass(frozen=True)
+class AugConfig:
+    """What one training crop may go through.  Spatial, with probability p_spatial per crop: three Euler angles uniform in +-rotate degrees (voxel
+    index space) and one log-uniform isotropic scale in `scale`.  Intensity, with probability p_intensity per channel: a gain uniform in `gain`, a
+    bias uniform in +-bias, a log-uniform gamma in `gamma` and a noise standard deviation uniform in [0, noise_std].  The default is all neutral."""
+    rotate: float = 0.0
+    scale: tuple = (1.0, 1.0)
+    p_spatial: float = 0.5
+    gain: tuple = (1.0, 1.0)
+    bias: float = 0.0
+    gamma: tuple = (1.0, 1.0)
+    noise_std: float = 0.0
+    p_intensity: float = 0.15
+
+    @classmethod
+    def defaults(cls, **over):
+        """What `--augment` alone turns on."""
+        return dataclasses.replace(cls(rotate=15.0, scale=(0.8, 1.25), p_spatial=0.5, gain=(0.75, 1.25), bias=0.1, gamma=(0.7, 1.5), noise_std=0.1,
+                                       p_intensity=0.15), **over)
+
+    @property
+    def spatial(self):
+        return self.p_spatial > 0 and (self.rotate != 0 or tuple(self.scale) != (1.0, 1.0))
+
+    @property
+    def intensity(self):
+        return self.p_intensity > 0 and (tuple(self.gain) != (1.0, 1.0) or self.bias != 0 or tuple(self.gamma) != (1.0, 1.0) or self.noise_std != 0)
+
+    @property
+    def enabled(self):
+        return self.spatial or self.intensity
+
+
+AUG_OPTIONS = ("aug_rotate", "aug_scale", "aug_gain", "aug_bias", "aug_gamma", "aug_noise", "aug_p_spatial", "aug_p_intensity")
+
+
+def _aug_number(flag, value, what):
+    try:
+        f = float(value)
+    except (TypeError, ValueError):
+        f = float("nan")
+    if f != f or f in (float("inf"), float("-inf")):
+        raise SystemExit(f"{flag} {value}: {what}")
+    return f
+
+
+def _aug_range(flag, value, what, positive=False):
+    try:
+        r = tuple(float(v) for v in (value.split(",") if isinstance(value, str) else value))
+    except (TypeError, ValueError):
+        r = ()
+    if len(r) != 2 or not all(np.isfinite(v) for v in r) or r[0] > r[1] or (positive and r[0] <= 0):
+        raise SystemExit(f"{flag} {value}: {what}")
+    return r
+
+
+def parse_aug(args):
+    """The augmentation options of `seg3d.py train` (absent attributes: not given) -> AugConfig, or None when none of them is given.  `--augment` turns
+    the defaults on; every override implies it and replaces one default.  A bad value exits with its message."""
+    given = {k: getattr(args, k, None) for k in AUG_OPTIONS}
+    given = {k: v for k, v in given.items() if v is not None}
+    if not given and not getattr(args, "augment", False):
+        return None
+    d = AugConfig.defaults()
+    rotate = _aug_number("--aug_rotate", given.get("aug_rotate", d.rotate), "the largest rotation about each axis in degrees, 0..45")
+    if not 0.0 <= rotate <= MAX_ROTATE:
+        raise SystemExit(f"--aug_rotate {given['aug_rotate']}: the largest rotation about each axis in degrees, 0..45 (beyond that the source box of a "
+                         "crop outgrows the crop several times)")
+    scale = _aug_range("--aug_scale", given.get("aug_scale", d.scale), "LO,HI with 0 < LO <= HI (the zoom factor is drawn log-uniformly between them)", True)
+    gain = _aug_range("--aug_gain", given.get("aug_gain", d.gain), "LO,HI with LO <= HI (the factor on a channel's intensities)")
+    gamma = _aug_range("--aug_gamma", given.get("aug_gamma", d.gamma), "LO,HI with 0 < LO <= HI (the exponent of sign(v) |v|^gamma)", True)
+    bias = _aug_number("--aug_bias", given.get("aug_bias", d.bias), "B >= 0 (a channel's intensities are shifted by a value in [-B, B])")
+    if bias < 0:
+        raise SystemExit(f"--aug_bias {given['aug_bias']}: B >= 0 (a channel's intensities are shifted by a value in [-B, B])")
+    noise = _aug_number("--aug_noise", given.get("aug_noise", d.noise_std), "STD >= 0 (the largest standard deviation of the added Gaussian noise)")
+    if noise < 0:
+        raise SystemExit(f"--aug_noise {given['aug_noise']}: STD >= 0 (the largest standard deviation of the added Gaussian noise)")
+    ps = []
+    for key, default in (("aug_p_spatial", d.p_spatial), ("aug_p_intensity", d.p_intensity)):
+        p = _aug_number("--" + key, given.get(key, default), "a probability in [0, 1]")
+        if not 0.0 <= p <= 1.0:
+            raise SystemExit(f"--{key} {given[key]}: a probability in [0, 1]")
+        ps.append(p)
+    return AugConfig(rotate=rotate, scale=scale, p_spatial=ps[0], gain=gain, bias=bias, gamma=gamma, noise_std=noise, p_intensity=ps[1])
+
+
+def _reach(a, b, theta):
+    """max over |t| <= theta of cos(t) a + sin|t| b, for a, b >= 0 and 0 <= theta <= pi / 2: the unconstrained maximum hypot(a, b) sits at
+    t = atan2(b, a); where that lies beyond theta the expression still rises at theta."""
+    return float(np.hypot(a, b)) if np.arctan2(b, a) <= theta else float(np.cos(theta) * a + np.sin(theta) * b)
+
+
+def source_extent(crop, cfg):
+    """The ONE source-box size (ex, ey, ez), even on every axis, of a loader with this crop and config: large enough that for every parameter set
+    the config can draw every trilinear corner of every output voxel lies inside the box.
+
+    Derivation.  The kernel samples output voxel i at s = M c + t + E / 2 - 0.5 with c = i + 0.5 - crop / 2, so |c_j| <= crop_j / 2 - 0.5, and
+    |t_i| <= 0.5.  The corners floor(s_i) and floor(s_i) + 1 are inside [0, E_i - 1] when 0 <= s_i < E_i - 1, that is when
+        |(M c)_i| + 0.5 < E_i / 2 - 0.5       which      E_i / 2 >= sum_j |M_ij| crop_j / 2 + 1 =: r_i + 1
+    guarantees (sum_j |M_ij| (crop_j / 2 - 0.5) + 0.5 < r_i + 0.5 whenever a row of M is not zero).  M = R F / z: F the diagonal of flip signs, which
+    |.| removes; z the zoom, largest inverse 1 / min(scale_lo, 1) (a crop that draws no spatial change has z = 1 and R = I, which the angle box
+    contains); R = Rx(a) Ry(b) Rz(g), every angle within +-theta, theta <= 45 degrees.  With h_j = crop_j / 2
+    and reach(A, B) = max_{|t| <= theta} cos(t) A + sin|t| B (_reach), the rows of R, entry by entry under the triangle inequality and every
+    angle maximised on its own:
+        row x = (cb cg, -cb sg, sb):                       cb (|cg| hx + |sg| hy) + |sb| hz  <=  reach(P, hz),   P = reach(hx, hy)
+        row z = sa (row y of Ry Rz) + ca (row z of Ry Rz):  ca (|sb| (|cg| hx + |sg| hy) + cb hz) + |sa| (|sg| hx + |cg| hy)
+                                                            <=  reach(U, Q),   U = reach(hz, P),   Q = reach(hy, hx)
+        row y = ca (row y of Ry Rz) - sa (row z of Ry Rz):  <=  reach(Q, U)
+    Row x's bound is attained; rows y and z are bounded from above (g is maximised separately in P and Q).  E_i is the smallest even integer
+    >= 2 (r_i / min(scale_lo, 1) + 1).  No rotation and no zoom: crop + 2."""
+    h = [float(c) / 2.0 for c in crop]
+    theta = np.deg2rad(min(max(float(cfg.rotate), 0.0), 90.0)) if cfg.p_spatial > 0 else 0.0
+    zoom = 1.0 / min(float(cfg.scale[0]), 1.0) if cfg.p_spatial > 0 else 1.0
+    P, Q = _reach(h[0], h[1], theta), _reach(h[1], h[0], theta)
+    U = _reach(h[2], P, theta)
+    rows = (_reach(P, h[2], theta), _reach(Q, U, theta), _reach(U, Q, theta))
+    # - 2^-20: a row sum that is an integer up to float64 rounding (no rotation: exactly crop / 2) must not cost two voxels; the inequality above has
+    # 0.5 sum_j |M_ij| >= 0.5 / max(scale_hi, 1) to spare
+    return tuple(2 * int(np.ceil(r * zoom + 1.0 - 2.0 ** -20)) for r in rows)
+
+
+def cut_box(case, start, extent):
+    """`cut` with starts allowed below 0: the extent-sized box at `start`, (x [C, *extent] in the case's dtype, lab uint8 [*extent]); what lies outside
+    the volume ON EITHER SIDE is image 0 / label 0x80.  A float16 case stays float16 up to the device (the kernel reads half).  An unlabelled case:
+    label 0 inside."""
+    C = case.img.shape[0]
+    x = np.zeros((C,) + tuple(extent), dtype=case.img.dtype)
+    lab = np.full(tuple(extent), NOT_COUNTED, dtype=np.uint8)
+    lo = [min(max(int(s), 0), n) for s, n in zip(start, case.shape)]
+    hi = [min(max(int(s) + int(e), 0), n) for s, e, n in zip(start, extent, case.shape)]
+    if all(b > a for a, b in zip(lo, hi)):
+        src = tuple(slice(a, b) for a, b in zip(lo, hi))
+        dst = tuple(slice(a - int(s), b - int(s)) for a, b, s in zip(lo, hi, start))
+        x[(slice(None),) + dst] = case.img[(slice(None),) + src]
+        lab[dst] = case.seg[src] if case.seg is not None else 0
+    return x, lab
+
+
+def rotation(angles):
+    """Rx(a) Ry(b) Rz(g) for angles in radians, float64 [3, 3]; axes in (x, y, z) voxel index order."""
+    (sa, sb, sg), (ca, cb, cg) = np.sin(angles), np.cos(angles)
+    rx = np.array([[1, 0, 0], [0, ca, -sa], [0, sa, ca]], dtype=np.float64)
+    ry = np.array([[cb, 0, sb], [0, 1, 0], [-sb, 0, cb]], dtype=np.float64)
+    rz = np.array([[cg, -sg, 0], [sg, cg, 0], [0, 0, 1]], dtype=np.float64)
+    return rx @ ry @ rz
+
+
+def inverse_affine(angles, scale, flips, crop, extent):
+    """The kernel's 12 numbers (rows (m0 m1 m2 t) of x, y, z), float32: M = R(angles) diag(flip signs) / scale -- the output crop is the resampled
+    box flipped, as draw_crop flips what it has cut -- and t = 0, or -0.5 on an axis where extent - crop is odd (the box then starts at
+    start - (extent - crop) // 2 and its centre sits half a voxel above the crop's)."""
+    m = rotation(np.asarray(angles, dtype=np.float64)) @ np.diag([-1.0 if f else 1.0 for f in flips]) / float(scale)
+    t = np.array([-0.5 if (int(e) - int(c)) % 2 else 0.0 for e, c in zip(extent, crop)])
+    return np.concatenate([m, t[:, None]], axis=1).reshape(12).astype(np.float32)
+
+
+def draw_aug_crop(rng, case, crop, centred, cfg, extent=None):
+    """One augmented training crop, still to be resampled on the device.  The crop is placed and flipped by draw_crop's rules with draw_crop's
+    draws (the same rng state gives the same start and flips); then, with probability p_spatial, three Euler angles and a zoom, and per channel with
+    probability p_intensity a gain, a bias, a gamma and a noise standard deviation (neutral values otherwise).
+    -> (src [C, *extent] in the case's dtype, src_lab uint8 [*extent], inv float32 [12], rows {'gain', 'bias', 'gamma', 'noise_std': float32 [C]},
+        info = draw_crop's {'start', 'flips', 'voxel'} plus 'box' (the box's start), 'angles' (radians), 'scale' and 'spatial' (whether drawn))"""
+    crop = tuple(int(c) for c in crop)
+    extent = source_extent(crop, cfg) if extent is None else tuple(int(e) for e in extent)
+    room = [max(n - c, 0) for n, c in zip(case.shape, crop)]
+    voxel = None
+    fg = case.foreground() if centred else ()
+    if len(fg):
+        voxel = tuple(int(v) for v in np.unravel_index(int(fg[int(rng.integers(len(fg)))]), case.shape))
+        start = tuple(min(max(v - c // 2, 0), r) for v, c, r in zip(voxel, crop, room))
+    else:
+        start = tuple(int(rng.integers(r + 1)) for r in room)
+    flips = tuple(bool(rng.integers(2)) for _ in range(3))
+    C = case.img.shape[0]
+    spatial = bool(rng.random() < cfg.p_spatial)
+    theta = np.deg2rad(float(cfg.rotate))
+    angles = rng.uniform(-theta, theta, 3)
+    scale = float(np.exp(rng.uniform(np.log(cfg.scale[0]), np.log(cfg.scale[1]))))
+    if not spatial:
+        angles, scale = np.zeros(3), 1.0
+    on = rng.random(C) < cfg.p_intensity
+    rows = {"gain": np.where(on, rng.uniform(cfg.gain[0], cfg.gain[1], C), 1.0), "bias": np.where(on, rng.uniform(-cfg.bias, cfg.bias, C), 0.0),
+            "gamma": np.where(on, np.exp(rng.uniform(np.log(cfg.gamma[0]), np.log(cfg.gamma[1]), C)), 1.0),
+            "noise_std": np.where(on, rng.uniform(0.0, cfg.noise_std, C), 0.0)}
+    rows = {k: v.astype(np.float32) for k, v in rows.items()}
+    box = tuple(s - (e - c) // 2 for s, c, e in zip(start, crop, extent))
+    src, src_lab = cut_box(case, box, extent)
+    info = {"start": start, "flips": flips, "voxel": voxel, "box": box, "angles": tuple(float(a) for a in angles), "scale": scale, "spatial": spatial}
+    return src, src_lab, inverse_affine(angles, scale, flips, crop, extent), rows, info
+
+
 class CropLoader:
     """`steps` batches of `b` training crops per epoch: (x float32 [b, C, *crop], lab uint8 [b, *crop]) host tensors.  The draws are a function of
-    (seed, rank, epoch) alone; crop i of a batch is centred on a labelled voxel for even i."""
+    (seed, rank, epoch) alone; crop i of a batch is centred on a labelled voxel for even i.
 
-    def __init__(self, cases, crop, b, steps, seed=0, rank=0):
+    With `aug` (an enabled AugConfig) a batch is (src [b, C, *extent] in the cases' dtype, src_lab uint8 [b, *extent], params): the source boxes of
+    draw_aug_crop and a dict of host tensors -- inv float32 [b, 12]; gain, bias, gamma, noise_std float32 [b, C]; seed, one int64 from the same
+    rng (the noise kernel's); crop int64 [3] -- that train_seg.train_step resamples on the device.  Without it: the code path and the random
+    stream of a loader that knows no augmentation."""
+
+    def __init__(self, cases, crop, b, steps, seed=0, rank=0, aug=None):
         if not cases:
             raise SystemExit("no training cases")
         self.cases, self.crop, self.b, self.steps, self.seed, self.rank, self.epoch = cases, tuple(crop), int(b), int(steps), int(seed), int(rank), 0
         self.sharded = True
+        self.aug = aug if aug is not None and aug.enabled else None
+        self.extent = source_extent(self.crop, self.aug) if self.aug is not None else None
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
@@ -225,8 +432,27 @@ class CropLoader:
     def __len__(self):
         return self.steps
 
+    def _augmented(self, rng):
+        for _ in range(self.steps):
+            srcs, labs, invs, rows = [], [], [], []
+            for i in range(self.b):
+                case = self.cases[int(rng.integers(len(self.cases)))]
+                src, lab, inv, row, _ = draw_aug_crop(rng, case, self.crop, i % 2 == 0, self.aug, self.extent)
+                srcs.append(src)
+                labs.append(lab)
+                invs.append(inv)
+                rows.append(row)
+            params = {k: torch.from_numpy(np.stack([r[k] for r in rows])) for k in ("gain", "bias", "gamma", "noise_std")}
+            params["inv"] = torch.from_numpy(np.stack(invs))
+            params["seed"] = torch.tensor(int(rng.integers(1 << 62)), dtype=torch.int64)
+            params["crop"] = torch.tensor(self.crop, dtype=torch.int64)
+            yield torch.from_numpy(np.stack(srcs)), torch.from_numpy(np.stack(labs)), params
+
     def __iter__(self):
         rng = np.random.default_rng([self.seed, self.rank, self.epoch])
+        if self.aug is not None:
+            yield from self._augmented(rng)
+            return
         for _ in range(self.steps):
             xs, ls = [], []
             for i in range(self.b):
@@ -305,5 +531,5 @@ def loaders(args, rank=0, world=1):
     else:
         raise SystemExit("--data must be 'synthetic' or a directory with <case>_img.npy / <case>_seg.npy and train.txt, val.txt, test.txt")
     steps = int(args.steps_per_epoch) or -(-len(train) // int(args.b))         # 0: one crop per training case and epoch
-    return {"train": CropLoader(train, crop, args.b, steps, args.seed, rank),
+    return {"train": CropLoader(train, crop, args.b, steps, args.seed, rank, aug=parse_aug(args)),
             "eval": TileLoader(val, crop, args.b, rank, world), "test": TileLoader(test, crop, args.b, rank, world)}

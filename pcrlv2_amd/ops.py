@@ -1953,3 +1953,58 @@ def filter_components(mask, labels, sizes, bit, keep_largest=False, min_voxels=0
         sizes = n          # an empty class: torch gives an empty view no address; with n == 0 the kernels read no size
     lib().call("pcrl_ccl_filter", mask, labels, sizes, n, out, bit, 1 if keep_largest else 0, min_voxels, workspace(nb, dev), nb, *shape, stream_handle())
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# joint image / label augmentation of segmentation training crops (csrc/seg_augment.hip)
+# ----------------------------------------------------------------------------------------------
+def seg_augment(src, src_lab, inv, gain, bias, out=None, crop=None):
+    """A batch of source boxes resampled into training crops in ONE launch (pcrl_seg_aug_resample): src [B, C, Sx, Sy, Sz] float32 / float16 and
+    src_lab uint8 [B, Sx, Sy, Sz] go through the same geometry inv float32 [B, 12] (the rows (m0 m1 m2 t) of x, y, z: output voxel, centred ->
+    source voxel, centred); the image trilinear with 0 outside the box, times gain plus bias (float32 [B, C] each); the label nearest neighbour
+    with 0x80 outside.  The crop's size comes from `out` = (x float32 [B, C, X, Y, Z], lab uint8 [B, X, Y, Z]), which then receives the result,
+    or from `crop` = (X, Y, Z).  -> (x, lab)"""
+    if (not torch.is_tensor(src) or src.dim() != 5 or src.dtype not in (torch.float32, torch.float16) or not src.is_contiguous() or not src.is_cuda
+            or src.numel() == 0):
+        got = f"{src.dtype} {tuple(src.shape)} on {src.device}" if torch.is_tensor(src) else type(src).__name__
+        raise PcrlError(f"seg_augment: src must be a contiguous non-empty float32 / float16 [B, C, Sx, Sy, Sz] tensor on the GPU, got {got}")
+    dev = src.device
+    B, C, Sx, Sy, Sz = (int(s) for s in src.shape)
+    if (not torch.is_tensor(src_lab) or src_lab.dtype != torch.uint8 or tuple(src_lab.shape) != (B, Sx, Sy, Sz) or not src_lab.is_contiguous()
+            or src_lab.device != dev):
+        raise PcrlError(f"seg_augment: src_lab must be a contiguous uint8 {(B, Sx, Sy, Sz)} tensor on {dev}")
+    for name, t, shape in (("inv", inv, (B, 12)), ("gain", gain, (B, C)), ("bias", bias, (B, C))):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise PcrlError(f"seg_augment: {name} must be a contiguous float32 {shape} tensor on {dev}")
+    if out is not None:
+        x, lab = out
+        crop = tuple(int(s) for s in x.shape[2:]) if torch.is_tensor(x) and x.dim() == 5 else ()
+    else:
+        try:
+            crop = tuple(int(c) for c in crop)
+        except (TypeError, ValueError):
+            crop = ()
+    if len(crop) != 3 or any(c < 1 for c in crop):
+        raise PcrlError("seg_augment: the crop's size comes from out = (x, lab) or from crop = (X, Y, Z), three positive sizes")
+    if out is None:
+        x = torch.empty((B, C) + crop, dtype=torch.float32, device=dev)
+        lab = torch.empty((B,) + crop, dtype=torch.uint8, device=dev)
+    elif (x.dtype != torch.float32 or tuple(x.shape) != (B, C) + crop or not x.is_contiguous() or x.device != dev or not torch.is_tensor(lab)
+          or lab.dtype != torch.uint8 or tuple(lab.shape) != (B,) + crop or not lab.is_contiguous() or lab.device != dev):
+        raise PcrlError(f"seg_augment: out must be (a contiguous float32 {(B, C) + crop} tensor, a contiguous uint8 {(B,) + crop} tensor) on {dev}")
+    lib().call("pcrl_seg_aug_resample", src, int(src.dtype == torch.float16), src_lab, x, lab, inv, gain, bias, B, C, Sx, Sy, Sz, *crop, stream_handle())
+    return x, lab
+
+
+def seg_noise_gamma(x, noise_std, gamma, seed):
+    """RandomNoise + RandomGamma of the pre-task loader (pcrl_aug_noise_gamma, csrc/augment.hip) on a batch of crops x float32 [B, C, X, Y, Z] with one
+    parameter pair per (sample, channel): noise_std, gamma float32 [B, C]; every channel is one of the kernel's B * C volumes.  -> a new tensor"""
+    if x.dim() != 5 or x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda or x.numel() == 0:
+        raise PcrlError(f"seg_noise_gamma: x must be a contiguous non-empty float32 [B, C, X, Y, Z] tensor on the GPU, got {x.dtype} {tuple(x.shape)}")
+    B, C = int(x.shape[0]), int(x.shape[1])
+    for name, t in (("noise_std", noise_std), ("gamma", gamma)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (B, C) or not t.is_contiguous() or t.device != x.device:
+            raise PcrlError(f"seg_noise_gamma: {name} must be a contiguous float32 {(B, C)} tensor on {x.device}")
+    y = torch.empty_like(x)
+    lib().call("pcrl_aug_noise_gamma", x, y, noise_std, gamma, B * C, x[0, 0].numel(), int(seed), stream_handle())
+    return y

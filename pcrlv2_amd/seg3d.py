@@ -1,6 +1,7 @@
 """3D segmentation on the pre-trained PCRLv2 network, decoder included: fine-tuning and prediction.
 
     python seg3d.py train   --data DIR --phase finetune --weights PRETRAIN.pt --n_class 3 --in_channels 4 --save_best --output OUT
+    python seg3d.py train   --data DIR --phase finetune --weights PRETRAIN.pt --n_class 3 --in_channels 4 --save_best --output OUT --augment
     python seg3d.py predict --data DIR --list test.txt --weights OUT/pcrlv2_seg3d_finetune_1.0_best.pt --out PRED
     python seg3d.py predict --data DIR --list test.txt --weights OUT/pcrlv2_seg3d_finetune_1.0_best.pt --out PRED --overlap 0.5 --window gaussian --probs
     python seg3d.py predict --data DIR --list test.txt --weights OUT/pcrlv2_seg3d_finetune_1.0_best.pt --out PRED --keep_largest all --min_voxels 8
@@ -16,7 +17,9 @@ distances in the units of --spacing (or of <case>_spacing.npy, three float64, wh
 DESIGN.md section 17).  `postprocess` cleans stored predictions by their connected components (6, 18 or 26 neighbours) into another directory that
 `score --pred` reads unchanged: the classes of --keep_largest keep only their largest component, and with --min_voxels N every class loses its
 components below N voxels; `predict` takes the same three options and cleans a mask on the device before it is written (csrc/components.hip,
-DESIGN.md section 18).  Without them `predict` writes what it always wrote.
+DESIGN.md section 18).  Without them `predict` writes what it always wrote.  `train --augment` (or any `--aug_*` option) resamples the training
+crops on the device -- rotation, zoom and flips of image channels and label bitmask in one kernel, then gain, bias, gamma and noise per channel
+(csrc/seg_augment.hip); without those options training does what it always did.
 """
 from __future__ import annotations
 
@@ -37,9 +40,10 @@ def check_train(args):
         raise SystemExit("--phase scratch starts from random weights: drop --weights or use --phase finetune")
     if args.b < 1 or args.epochs < 1 or args.steps_per_epoch < 0:
         raise SystemExit("--b and --epochs must be positive, --steps_per_epoch non-negative")
-    from .data_seg import check_overlap, check_window
+    from .data_seg import check_overlap, check_window, parse_aug
     check_overlap(args.val_overlap, "--val_overlap")
     check_window(args.val_window, "--val_window")
+    parse_aug(args)
 
 
 def train(args):
@@ -114,6 +118,16 @@ def build_parser():
     tr.add_argument("--val_overlap", type=float, default=0.0, help="validation and the final test by sliding windows that overlap by this fraction of "
                     "the crop, blended (0..0.75); 0 = stride-tiled patches")
     tr.add_argument("--val_window", default="gaussian", help="blending window with --val_overlap > 0: gaussian | constant")
+    tr.add_argument("--augment", action="store_true", help="resample the training crops on the device: rotation, zoom, gain, bias, gamma and noise at "
+                    "the defaults of the --aug_* options; each of those implies it")
+    tr.add_argument("--aug_rotate", default=None, help="largest rotation about each axis in degrees, 0..45 (15)")
+    tr.add_argument("--aug_scale", default=None, help="LO,HI of the log-uniform isotropic zoom (0.8,1.25)")
+    tr.add_argument("--aug_gain", default=None, help="LO,HI of the factor on a channel's intensities (0.75,1.25)")
+    tr.add_argument("--aug_bias", default=None, help="a channel's intensities are shifted by a value in [-B, B] (0.1)")
+    tr.add_argument("--aug_gamma", default=None, help="LO,HI of the log-uniform exponent of sign(v) |v|^gamma (0.7,1.5)")
+    tr.add_argument("--aug_noise", default=None, help="largest standard deviation of the added Gaussian noise (0.1)")
+    tr.add_argument("--aug_p_spatial", default=None, help="probability that a crop is rotated and zoomed (0.5)")
+    tr.add_argument("--aug_p_intensity", default=None, help="probability, per channel, that its intensities are changed (0.15)")
     tr.set_defaults(model="pcrlv2", n="seg3d", ratio=1.0)
     pr = sub.add_parser("predict", help="write <case>_pred.npy (uint8 bitmask) for every case of a list")
     pr.add_argument("--data", required=True, help="directory with <case>_img.npy")

@@ -17,6 +17,10 @@ distance transforms and the order statistics on the device (csrc/surface_dist.hi
 
 `seg3d.py postprocess` and the clean-up options of `predict` (postprocess_mask, postprocess) drop connected components of a mask's
 classes on the device (csrc/components.hip): all but the largest, and / or those below a volume.
+
+`seg3d.py train --augment` (augment_batch): the loader hands over source boxes and drawn parameters, and the step's forward
+resamples image channels and label bitmask together on the device (csrc/seg_augment.hip), then adds noise and gamma (csrc/augment.hip).  Evaluation,
+prediction and the sliding window never see it.
 """
 from __future__ import print_function
 
@@ -64,9 +68,31 @@ def higher_dice(val, best):
     return m == m and (best is None or m > best["mean_dice"])
 
 
+def is_augmented(batch):
+    """A batch of data_seg.CropLoader(aug=...): (source boxes, their labels, the dict of drawn parameters)."""
+    return len(batch) == 3 and isinstance(batch[2], dict)
+
+
+def augment_batch(batch, device=None):
+    """The device side of an augmented batch (src [B,C,*extent] float32 / float16, src_lab uint8 [B,*extent], params -- host tensors): upload, ONE
+    ops.seg_augment launch for image and labels, then pcrl_aug_noise_gamma over the B * C channels when any noise_std != 0 or gamma != 1 (decided on
+    the host tensors; skipped otherwise, so neutral intensity is bit-identical to the resampling alone).  On the current stream.
+    -> (x float32 [B,C,*crop], lab uint8 [B,*crop])"""
+    src, src_lab, p = batch
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    up = lambda t: t.to(dev, non_blocking=True)      # noqa: E731  (a float16 source stays float16: the kernel reads half)
+    x, lab = _ops.seg_augment(up(src), up(src_lab), up(p["inv"]), up(p["gain"]), up(p["bias"]), crop=tuple(int(c) for c in p["crop"]))
+    if bool((p["noise_std"] != 0).any()) or bool((p["gamma"] != 1).any()):
+        x = _ops.seg_noise_gamma(x, up(p["noise_std"]), up(p["gamma"]), int(p["seed"]))
+    return x, lab
+
+
 def train_step(model, optimizer, batch):
-    """One optimisation step on (x [B,C,X,Y,Z] float32, labels uint8 [B,X,Y,Z]).  -> (loss, sums), detached."""
+    """One optimisation step on (x [B,C,X,Y,Z] float32, labels uint8 [B,X,Y,Z]), or on an augmented batch (is_augmented), which augment_batch turns
+    into that inside the step's forward.  -> (loss, sums), detached."""
     def forward():
+        if is_augmented(batch):
+            return model.loss(*augment_batch(batch))
         x = to_gpu(batch[0])
         return model.loss(x, batch[1].to(x.device, non_blocking=True))
 
