@@ -1,5 +1,5 @@
 """Exactly summable operands: the helper of the bit-for-bit convolution tests (test_exact_lattice_cpu.py, test_conv2d_exact_gpu.py,
-test_conv3d_exact_gpu.py).  Not a test file.
+test_conv3d_exact_gpu.py, test_conv_to1_exact_gpu.py, test_convt_exact_gpu.py, test_upconv_exact_gpu.py).  Not a test file.
 
 Operands drawn from a small dyadic lattice (integers / a power of two) are exactly representable in bf16, every product of two of them is exact in
 float32, and every partial sum of such products -- in any order, over any split -- is an integer multiple of one fixed unit.  While the sum of the

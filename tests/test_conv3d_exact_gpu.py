@@ -4,8 +4,9 @@ under every conv test-hook code defined for the shape, pcrl_conv3d_k3_fwd_affine
 and pcrl_conv3d_k3_wgrad under the impl / tr pairs of tests/test_ops_gpu.py::test_conv3d_fwd_stats_dgrad_wgrad.
 
 The one-channel convolutions and the transposed convolution are pinned the same way by tests/test_conv_to1_exact_gpu.py and
-tests/test_convt_exact_gpu.py (cases: tests/conv1_cases.py).  Out of scope of the lattice method: the composed up-convolution (its phase weights are
-float32 sums of products and leave the lattice; tests/test_mfma_pin_gpu.py owns it)."""
+tests/test_convt_exact_gpu.py (cases: tests/conv1_cases.py), and the composed up-convolution by tests/test_upconv_exact_gpu.py (cases:
+tests/upconv_cases.py): its phase weights are sums of products of the two layers' weights, and a sparse transposed convolution keeps them on a lattice
+of bf16 values."""
 import collections
 import functools
 import types
