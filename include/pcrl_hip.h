@@ -887,6 +887,48 @@ int pcrl_ccl_filter(const uint8_t* mask, const int* labels, const int* sizes, co
 int pcrl_seg_aug_resample(const void* src, int src_half, const uint8_t* src_lab, float* y, uint8_t* lab, const float* inv, const float* gain,
                           const float* bias, int B, int C, int Sx, int Sy, int Sz, int X, int Y, int Z, pcrl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * 3D path, preparation of raw volumes into the segmenter's cases and the way back (csrc/seg_prep.hip, -ffp-contract=off).
+ *   Sources stay in DISK order: src [C][Z][Y][X], x fastest, int16 (src_kind = 0) or float32 (src_kind = 1); src_lab uint8 [Z][Y][X].  Outputs are in
+ *   project order, z fastest.  The mask M of a voxel is (any channel != 0).  Common refusals, PCRL_EINVAL before any launch: a null or overlapping
+ *   buffer, C outside 1..16, K outside 1..7, an extent < 1, a grid of 2^31 voxels or more.  Integer atomics only; every output element is written
+ *   once: two runs give identical bytes.
+ * pcrl_segprep_scan -- rec int64 [8] = {x0, x1, y0, y1, z0, z1, |M|, non-finite values}: the half-open bounding box of M (empty: every lower
+ *   bound 0x7fffffff, every upper bound 0), the voxels of M and the count of NaN / +-inf over all channels.
+ * pcrl_segprep_stats -- stats float64 [C][2] = {mean, population standard deviation} of min(max(x, lo), hi) over M (use_mask != 0; n = rec[6], rec as
+ *   pcrl_segprep_scan wrote it) or over every voxel (use_mask = 0; rec may be NULL).  clip float64 [C][2] = {lo, hi} or NULL (no clip).  Two passes,
+ *   sum(x) / n then sqrt(sum((x - mean)^2) / n), per-block partials added in block order by a one-block launch: a function of the sizes and the data.
+ *   ws: pcrl_segprep_stats_ws_bytes(C, X * Y * Z), 8-byte aligned.
+ * pcrl_segprep_select -- out float32 [4]: the EXACT order statistics at ranks r0..r3 (0-based, ascending order) of channel ch over M (use_mask != 0)
+ *   or over every voxel; -0.0 counts as +0.0 and is returned as +0.0.  A radix select on order-preserving 32-bit keys, four byte passes.
+ *   ws: pcrl_segprep_select_ws_bytes(), 8-byte aligned.
+ * pcrl_segprep_resample -- ONE launch: the box [bx, bx + NX) x [by, by + NY) x [bz, bz + NZ) of the source -> img [C][OX][OY][OZ] float32
+ *   (out_half = 0) or float16 (out_half = 1) and lab uint8 [OX][OY][OZ].  Tables, built by the host in float64, indices relative to the box:
+ *       tab_i int32   i0, i1, nn of x [3][OX], then of y [3][OY], then of z [3][OZ]          tab_w float64   w0, w1 of x [2][OX], y [2][OY], z [2][OZ]
+ *   Per output voxel and channel, float64, one operation at a time (v: a corner's value, widened exactly):
+ *       u   = (min(max(v, lo), hi) - mean) / max(std, 1e-8)     0.0 where use_mask != 0 and the corner is outside M
+ *       acc = 0.0;  for x in (i0, i1): for y in (i0, i1): for z in (i0, i1):  acc = acc + ((u * wx) * wy) * wz
+ *   and ONE rounding of acc to the output type (float16 as well: csrc/seg_prep.hip).  stats float64 [C][2] {mean, std} or NULL (0, 1); clip float64
+ *   [C][2] {lo, hi} or NULL (-inf, +inf).  lab = region[src_lab[nn_z][nn_y][nn_x]], region uint8 [256]; src_lab NULL (an unlabelled case): lab = 0
+ *   and region may be NULL.  K = the number of regions (bits 0..K-1 of region's entries).  Every table entry is clamped to the box inside the kernel.
+ *   pcrl_segprep_resample_tile: the output tile (along x and z; one y) and the LDS bytes a launch with these box and output extents uses (host function).
+ * pcrl_segprep_restore -- pred uint8 [PX][PY][PZ] (the prepared grid) -> out uint8 [X][Y][Z]: inside the box out = pred[nn_x][nn_y][nn_z] with
+ *   tab int32 = nn of x [NX], y [NY], z [NZ] (prepared indices of the box's voxels, clamped in the kernel), 0 outside.  painted uint8 [X][Y][Z] or
+ *   NULL: paint[out], paint uint8 [256]. */
+int pcrl_segprep_scan(const void* src, int src_kind, int C, int X, int Y, int Z, int64_t* rec, pcrl_stream_t stream);
+size_t pcrl_segprep_stats_ws_bytes(int C, int64_t V);
+int pcrl_segprep_stats(const void* src, int src_kind, int C, int X, int Y, int Z, int use_mask, const int64_t* rec, const double* clip, double* stats,
+                       void* ws, size_t ws_bytes, pcrl_stream_t stream);
+size_t pcrl_segprep_select_ws_bytes(void);
+int pcrl_segprep_select(const void* src, int src_kind, int C, int ch, int X, int Y, int Z, int use_mask, int64_t r0, int64_t r1, int64_t r2, int64_t r3,
+                        float* out, void* ws, size_t ws_bytes, pcrl_stream_t stream);
+int pcrl_segprep_resample_tile(int NX, int NZ, int OX, int OZ, int use_mask, int* tx, int* tz, int64_t* lds_bytes);
+int pcrl_segprep_resample(const void* src, int src_kind, const uint8_t* src_lab, int C, int X, int Y, int Z, int bx, int by, int bz, int NX, int NY,
+                          int NZ, const int32_t* tab_i, const double* tab_w, const double* stats, const double* clip, const uint8_t* region, int K,
+                          int use_mask, void* img, int out_half, uint8_t* lab, int OX, int OY, int OZ, pcrl_stream_t stream);
+int pcrl_segprep_restore(const uint8_t* pred, int PX, int PY, int PZ, const int32_t* tab, int bx, int by, int bz, int NX, int NY, int NZ,
+                         const uint8_t* paint, uint8_t* out, uint8_t* painted, int X, int Y, int Z, pcrl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

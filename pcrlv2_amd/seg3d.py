@@ -20,6 +20,12 @@ components below N voxels; `predict` takes the same three options and cleans a m
 DESIGN.md section 18).  Without them `predict` writes what it always wrote.  `train --augment` (or any `--aug_*` option) resamples the training
 crops on the device -- rotation, zoom and flips of image channels and label bitmask in one kernel, then gain, bias, gamma and noise per channel
 (csrc/seg_augment.hip); without those options training does what it always did.
+
+    python seg3d.py prepare --data RAW --manifest cases.tsv --save DIR --regions "1,2,4;1,4;4" --spacing 1,1,1 --split 0.7,0.1,0.2 --seed 0
+    python seg3d.py restore --prep DIR --pred PRED --list DIR/test.txt --out ORIG --paint "2,1,4" --nifti
+
+`prepare` writes DIR from raw NIfTI-1 / .npy volumes (crop to the non-zero box, per-case normalisation, resampling to a common spacing, label values
+to the bitmask) and `restore` takes stored predictions back to the original grid (pcrlv2_amd/seg_prep.py, csrc/seg_prep.hip).
 """
 from __future__ import annotations
 
@@ -83,6 +89,20 @@ def postprocess(args):
     exits with its message in train_seg.postprocess_plan, before anything touches a GPU."""
     from .train_seg import postprocess as run
     return run(args)
+
+
+def prepare(args):
+    """Every refusal (regions, spacing, the normalisation's options, the manifest and its files) exits with its message in seg_prep.check_prepare,
+    before anything touches a GPU."""
+    from .seg_prep import run
+    return run(args)
+
+
+def restore(args):
+    """Every refusal (--paint, a missing or mis-shaped prediction, a missing <case>_prep.npz, --out equal to --pred) exits with its message in
+    seg_prep.check_restore, before anything touches a GPU."""
+    from .seg_prep import run_restore
+    return run_restore(args)
 
 
 def _cleanup_options(p):
@@ -158,12 +178,37 @@ def build_parser():
     sc.add_argument("--spacing", default="1,1,1", help="voxel size sx,sy,sz; a case's <case>_spacing.npy replaces it")
     sc.add_argument("--csv", default="", help="also write case,class,dice,hd95,hd,assd,n_pred,n_gt to this file")
     sc.add_argument("--gpu", type=int, default=0)
+    pe = sub.add_parser("prepare", help="raw NIfTI / .npy volumes -> <case>_img.npy, <case>_seg.npy, <case>_spacing.npy, <case>_prep.npz")
+    pe.add_argument("--data", required=True, help="directory the manifest's paths are relative to")
+    pe.add_argument("--manifest", required=True, help="one case per line: name seg_path|- img_path [img_path ...]")
+    pe.add_argument("--save", required=True, help="output directory (the --data of train / predict / score)")
+    pe.add_argument("--regions", required=True, help="K = 1..7 sets of label values, bit k = set k: \"1,2,4;1,4;4\"")
+    pe.add_argument("--spacing", default="keep", help="target voxel size sx,sy,sz, or `keep`")
+    pe.add_argument("--crop_nonzero", type=int, default=1, help="1: crop to the bounding box of the non-zero voxels and normalise over them; 0: neither")
+    pe.add_argument("--norm", default="zscore", help="zscore | percentile | window | none")
+    pe.add_argument("--percentiles", default=None, help="LO,HI of --norm percentile: clip to these percentiles of the case (0.5,99.5)")
+    pe.add_argument("--window", default=None, help="LO,HI of --norm window: clip to this intensity window")
+    pe.add_argument("--mean", type=float, default=None, help="--norm window: subtracted after the clip")
+    pe.add_argument("--std", type=float, default=None, help="--norm window: divided by after the clip")
+    pe.add_argument("--float16", action="store_true", help="write float16 images (half the disk; the loader reads either)")
+    pe.add_argument("--split", default=None, help="train,val,test fractions: also write train.txt / val.txt / test.txt")
+    pe.add_argument("--seed", type=int, default=None, help="seed of --split")
+    pe.add_argument("--writers", type=int, default=4, help="file-writing threads (at most 16)")
+    pe.add_argument("--gpu", type=int, default=0)
+    rs = sub.add_parser("restore", help="<case>_pred.npy from the prepared grid back to the original grid")
+    rs.add_argument("--prep", required=True, help="the --save of `prepare` (<case>_prep.npz)")
+    rs.add_argument("--pred", required=True, help="directory with <case>_pred.npy on the prepared grid (the --out of `predict`)")
+    rs.add_argument("--list", required=True, help="file of case names (in --prep, or a path)")
+    rs.add_argument("--out", required=True, help="output directory; not --pred")
+    rs.add_argument("--paint", default=None, help="also write <case>_label.npy: class k painted with the k-th value, later over earlier: \"2,1,4\"")
+    rs.add_argument("--nifti", action="store_true", help="also write .nii.gz with the stored header's geometry")
+    rs.add_argument("--gpu", type=int, default=0)
     return ap
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    return {"train": train, "predict": predict, "score": score, "postprocess": postprocess}[args.command](args)
+    return {"train": train, "predict": predict, "score": score, "postprocess": postprocess, "prepare": prepare, "restore": restore}[args.command](args)
 
 
 if __name__ == "__main__":
