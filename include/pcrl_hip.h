@@ -800,10 +800,25 @@ int pcrl_seg_head_eval(const void* a, const float* w, const float* b, const uint
  *            voxels, the loss of the head's formula; per-block float64 partials and the head's fixed-order second launch.  ws: pcrl_seg_blend_ws_bytes.
  *     counts int64 [K][3] (with sums only): {TP, |pred|, |gt|} ADDED to this one row of a counts table with 64-bit integer atomics.
  *   No floating-point atomics: two runs give identical bytes.
- *   PCRL_EINVAL for K outside 1..7, an empty volume or crop, and P != nx * ny * nz. */
+ *   PCRL_EINVAL for K outside 1..7, an empty volume or crop, and P != nx * ny * nz.
+ * Mirror test-time augmentation and checkpoint ensembles: every further set of per-patch logits is ADDED into z, un-mirrored, so the buffer keeps its
+ *   size.  A mirror code `flip` in 0..7 has bit 0 = x, bit 1 = y, bit 2 = z: the patch's first, second and third spatial axis (z is the fastest).
+ * pcrl_seg_cut_patches_mirror -- pcrl_seg_cut_patches' output with the patch BOX mirrored along the axes of flip, the zeros it has outside the
+ *   volume included: out[p][c][i][j][k] = patch[p][c][fx ? cx-1-i : i][fy ? cy-1-j : j][fz ? cz-1-k : k].  flip = 0 gives pcrl_seg_cut_patches' bytes.
+ *   PCRL_EINVAL for flip outside 0..7 and for whatever pcrl_seg_cut_patches refuses.
+ * pcrl_seg_head_logits_acc -- pcrl_seg_head_logits of a sample grid cx x cy x cz (S = cx * cy * cz) whose input was mirrored by flip: the logit zk of
+ *   voxel s = (i * cy + j) * cz + k of sample n (bit-identical to pcrl_seg_head_logits') goes to the un-mirrored voxel
+ *   s' = ((fx ? cx-1-i : i) * cy + (fy ? cy-1-j : j)) * cz + (fz ? cz-1-k : k):
+ *       v = first ? zk : z[n][s'][sub] + zk;   z[n][s'][sub] = v * scale;        plain float32: one add, one multiply, in this order
+ *   Every element of z is read and written by exactly one thread: no atomics, two runs give identical bytes.  No workspace.
+ *   PCRL_EINVAL for flip outside 0..7, S != cx * cy * cz, and whatever pcrl_seg_head_logits refuses. */
 int pcrl_seg_head_logits(const void* a, const float* w, const float* b, float* z, int N, int64_t S, int K, int dtype, pcrl_stream_t stream);
 int pcrl_seg_cut_patches(const void* img, int src_half, const int* starts, float* out, int n, int C, int X, int Y, int Z, int cx, int cy, int cz,
                          pcrl_stream_t stream);
+int pcrl_seg_cut_patches_mirror(const void* img, int src_half, const int* starts, float* out, int n, int C, int X, int Y, int Z, int cx, int cy, int cz,
+                                int flip, pcrl_stream_t stream);
+int pcrl_seg_head_logits_acc(const void* a, const float* w, const float* b, float* z, int N, int64_t S, int K, int dtype, int cx, int cy, int cz, int flip,
+                             int first, float scale, pcrl_stream_t stream);
 size_t pcrl_seg_blend_ws_bytes(int X, int Y, int Z);
 int pcrl_seg_blend(const float* z, int64_t P, const int* sx, const int* sy, const int* sz, int nx, int ny, int nz, const float* wx, const float* wy,
                    const float* wz, int cx, int cy, int cz, int X, int Y, int Z, int K, const uint8_t* labels, uint8_t* mask, float* probs, float* numden,

@@ -19,6 +19,10 @@
 //           once per instruction -- conflict-free.  There is no LDS traffic inside the voxel loop.
 // cut       a pure copy: thread = 4 consecutive z of one (patch, channel, x, y) row; four scalar loads (the source run starts at any z), one 16-byte
 //           store; what lies outside the volume is 0, and float16 sources are widened exactly.
+// mirror    the cutter's sibling for mirror test-time augmentation (seg_cut_patches_mirror; flip bit 0 = x, bit 1 = y, bit 2 = z): the same thread ->
+//           output mapping and the same 16-byte store; the patch BOX is mirrored, its zeros outside the volume included.  An x / y mirror moves
+//           whole source rows; with a z mirror a thread's four scalar loads run backwards, and the 64 threads of a wave still read one contiguous
+//           span of source rows (the same cache lines, in reverse).
 #include "internal.h"
 
 namespace {
@@ -191,6 +195,37 @@ __global__ void __launch_bounds__(SB_THREADS) seg_cut_kernel(const T* __restrict
   *reinterpret_cast<float4*>(out + q * 4) = o;
 }
 
+// The cutter's mirrored sibling, same grid and same thread -> output mapping: output voxel (i, j, k) of a patch is voxel (fx ? cx-1-i : i,
+// fy ? cy-1-j : j, fz ? cz-1-k : k) of the patch BOX, zeros outside the volume included.  With a z-mirror the four scalar loads of a thread run backwards.
+template <typename T>
+__global__ void __launch_bounds__(SB_THREADS) seg_cut_mirror_kernel(const T* __restrict__ img, const int* __restrict__ starts, float* __restrict__ out,
+                                                                   int64_t total, int C, int X, int Y, int Z, int cx, int cy, int cz, int flip) {
+  const int64_t q = (int64_t)blockIdx.x * SB_THREADS + threadIdx.x;
+  if (q >= total) return;
+  const int cz4 = cz >> 2;
+  const int k4 = (int)(q % cz4);
+  int64_t r = q / cz4;
+  const int j = (int)(r % cy);
+  r /= cy;
+  const int i = (int)(r % cx);
+  r /= cx;
+  const int c = (int)(r % C);
+  const int64_t p = r / C;
+  const int pi = (flip & 1) ? cx - 1 - i : i, pj = (flip & 2) ? cy - 1 - j : j;
+  const int pk0 = (flip & 4) ? cz - 1 - 4 * k4 : 4 * k4, dk = (flip & 4) ? -1 : 1;
+  const int64_t x = (int64_t)starts[p * 3] + pi, y = (int64_t)starts[p * 3 + 1] + pj, z0 = (int64_t)starts[p * 3 + 2] + pk0;
+  const bool row_in = x >= 0 && x < X && y >= 0 && y < Y;
+  const T* __restrict__ src = img + (((int64_t)c * X + (row_in ? x : 0)) * Y + (row_in ? y : 0)) * Z;
+  float4 o;
+  float* ov = reinterpret_cast<float*>(&o);
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int64_t zz = z0 + dk * u;
+    ov[u] = (row_in && zz >= 0 && zz < Z) ? (float)src[zz] : 0.0f;
+  }
+  *reinterpret_cast<float4*>(out + q * 4) = o;
+}
+
 }  // namespace
 
 extern "C" size_t pcrl_seg_blend_ws_bytes(int X, int Y, int Z) {
@@ -247,4 +282,23 @@ extern "C" int pcrl_seg_cut_patches(const void* img, int src_half, const int* st
     hipLaunchKernelGGL(seg_cut_kernel<float>, dim3((unsigned)blocks), dim3(SB_THREADS), 0, st, static_cast<const float*>(img), starts, out, total, C, X, Y, Z, cx,
                        cy, cz);
   return pcrl_check_launch("seg_cut_patches");
+}
+
+extern "C" int pcrl_seg_cut_patches_mirror(const void* img, int src_half, const int* starts, float* out, int n, int C, int X, int Y, int Z, int cx, int cy,
+                                           int cz, int flip, pcrl_stream_t stream) {
+  PCRL_REQUIRE(flip >= 0 && flip <= 7, "seg_cut_patches_mirror: flip %d is no mirror code (bit 0 = x, bit 1 = y, bit 2 = z: 0..7)", flip);
+  PCRL_REQUIRE(img && starts && out, "seg_cut_patches_mirror: null pointer");
+  PCRL_REQUIRE(reinterpret_cast<uintptr_t>(out) % 16 == 0, "seg_cut_patches_mirror: out must be 16-byte aligned (16-byte stores)");
+  PCRL_REQUIRE(n > 0 && C > 0 && X > 0 && Y > 0 && Z > 0, "seg_cut_patches_mirror: bad sizes n=%d C=%d volume %d x %d x %d", n, C, X, Y, Z);
+  PCRL_REQUIRE(cx > 0 && cy > 0 && cz > 0 && cz % 4 == 0, "seg_cut_patches_mirror: bad crop %d x %d x %d (cz is a multiple of 4)", cx, cy, cz);
+  const int64_t total = (int64_t)n * C * cx * cy * (cz / 4), blocks = (total + SB_THREADS - 1) / SB_THREADS;
+  PCRL_REQUIRE(blocks < ((int64_t)1 << 31), "seg_cut_patches_mirror: too many output voxels in one call");
+  hipStream_t st = as_stream(stream);
+  if (src_half)
+    hipLaunchKernelGGL(seg_cut_mirror_kernel<_Float16>, dim3((unsigned)blocks), dim3(SB_THREADS), 0, st, static_cast<const _Float16*>(img), starts, out, total,
+                       C, X, Y, Z, cx, cy, cz, flip);
+  else
+    hipLaunchKernelGGL(seg_cut_mirror_kernel<float>, dim3((unsigned)blocks), dim3(SB_THREADS), 0, st, static_cast<const float*>(img), starts, out, total, C, X,
+                       Y, Z, cx, cy, cz, flip);
+  return pcrl_check_launch("seg_cut_patches_mirror");
 }

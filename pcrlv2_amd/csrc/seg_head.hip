@@ -17,6 +17,17 @@
 // logits    the same read of a and the same sh_logit, nothing else: lane sub < K of a voxel stores z_k as float32 at z[voxel][sub].  The voxels of a
 //           wave are consecutive, so a store instruction writes one contiguous run of (64 / LPV) * K floats.  No LDS, no sums, no workspace.  This is
 //           what overlap-blended sliding windows (seg_blend.hip) average; a logit is bit-identical to the one the eval kernel thresholds.
+// logits+   the accumulating sibling for mirror test-time augmentation and checkpoint ensembles (seg_head_logits_acc): the network saw the patch mirrored
+//           along the axes of `flip`, so the logit of voxel s = (i, j, k) belongs to the un-mirrored voxel s' = (fx ? cx-1-i : i, fy ? cy-1-j : j,
+//           fz ? cz-1-k : k).  The read of a, sh_fetch and sh_logit are the plain kernel's; the store is v = first ? z_k : z[s'][sub] + z_k, then
+//           z[s'][sub] = v * scale (one add, one multiply, plain float32).  What a wave sees: its 64 / LPV voxels are consecutive along z, so without a
+//           z mirror it stores the plain kernel's one contiguous run of (64 / LPV) * K floats, moved as a whole by an x / y mirror (rows of cz voxels
+//           keep their inside and change places); with a z mirror the runs of K floats of the wave's consecutive voxels are the SAME addresses in
+//           reverse voxel order (a wave whose voxels cross the end of a z row has two such runs, one per row) -- the same cache lines, each
+//           written once in full.  The added read of z (not on a first pass) has exactly the store's addresses, one pass earlier:
+//           it is issued one iteration ahead next to the prefetch of a, and reads (64 / LPV) * K floats per wave where the row of a is 64 / LPV
+//           vectors of 256 (128) bytes, i.e. K / 16 (K / 8) of the bytes the kernel reads anyway.  s -> s' is a bijection of the sample's voxels and
+//           lane sub of voxel s alone touches z[s'][sub]: no atomics, no LDS, no workspace, two runs give identical bytes.
 // The weight lives in registers: lane `sub` holds W[k][sub * V .. sub * V + V) for every k (K * V floats), read once per block from global memory.
 // LDS is used only for the block-level combination at the end of a block: red[wave][slot] (float64), redc[wave][k * 3 + q] (integers) and
 // redw[wave][k * 64 + c] (float32).  Writers are the first LPV lanes of each wave: one scalar store per (k, j), lane `sub` at word k * 64 + sub * V + j,
@@ -346,6 +357,68 @@ __global__ void __launch_bounds__(SH_THREADS) seg_head_logits_kernel(const T* __
   }
 }
 
+struct ShMirror {
+  int cx, cy, cz, flip;      // the sample's grid (S = cx * cy * cz, z fastest) and the mirror code: bit 0 = x, bit 1 = y, bit 2 = z
+};
+
+// float index in z of class `sub` at the un-mirrored voxel of (i, j, k) of the sample that starts at voxel `base`
+__device__ __forceinline__ int64_t sh_unmirrored(const ShMirror& m, int64_t base, int i, int j, int k, int K, int sub) {
+  const int ii = (m.flip & 1) ? m.cx - 1 - i : i, jj = (m.flip & 2) ? m.cy - 1 - j : j, kk = (m.flip & 4) ? m.cz - 1 - k : k;
+  return (base + ((int64_t)ii * m.cy + jj) * m.cz + kk) * K + sub;
+}
+
+// grid = (gx, N); block = 256.  The logits kernel with an un-mirroring, accumulating store: lane sub < K of voxel s = (i, j, k) owns z[n][s'][sub] at the
+// un-mirrored voxel s', reads it (unless FIRST), adds its logit and stores the sum times `scale`.  s -> s' is a bijection of the sample's voxels, so
+// every element of z is read and written by this one lane of the call.  (i, j, k) is divided out once and then advanced by the block stride with carries.
+template <typename T, int K, bool FIRST>
+__global__ void __launch_bounds__(SH_THREADS) seg_head_logits_acc_kernel(const T* __restrict__ a, const float* __restrict__ W, const float* __restrict__ bias,
+                                                                        float* z, int S, ShMirror m, float scale) {
+  constexpr int V = Vec16<T>::N, LPV = 64 / V, GPB = SH_THREADS / LPV;
+  const int t = threadIdx.x, sub = t % LPV, grp = t / LPV;
+  const int64_t base = (int64_t)blockIdx.y * S;
+  float w[K][V];
+  sh_load_w<T, K>(W, sub, w);
+  const float bk = sub < K ? bias[sub] : 0.0f;
+  const int iters = (S + GPB - 1) / GPB, step = gridDim.x;
+  const int adv = step * GPB, plane = m.cy * m.cz;      // voxels between two iterations of a thread (<= 1024 * 32)
+  const int dk = adv % m.cz, dj = (adv / m.cz) % m.cy, di = adv / plane;
+  Vec16<T> x;
+  unsigned lab;
+  int it = blockIdx.x;
+  int s = it < iters ? it * GPB + grp : S;
+  int k = s % m.cz, j = (s / m.cz) % m.cy, i = s / plane;
+  sh_fetch<T>(a, nullptr, base, s, S, sub, x, lab);
+  float zo = 0.0f;
+  if (!FIRST && sub < K && s < S) zo = z[sh_unmirrored(m, base, i, j, k, K, sub)];
+  for (; it < iters; it += step) {
+    const int sn = it + step < iters ? s + adv : S;
+    int kn = k + dk, jn = j + dj, in = i + di;
+    if (kn >= m.cz) {
+      kn -= m.cz;
+      ++jn;
+    }
+    if (jn >= m.cy) {
+      jn -= m.cy;
+      ++in;
+    }
+    Vec16<T> xn;
+    sh_fetch<T>(a, nullptr, base, sn, S, sub, xn, lab);
+    float zn = 0.0f;      // the next voxel's element is not the one stored below (the bijection), so it may be read ahead of that store
+    if (!FIRST && sub < K && sn < S) zn = z[sh_unmirrored(m, base, in, jn, kn, K, sub)];
+    const float zk = sh_logit<T, K>(x, w, bk, sub);
+    if (sub < K && s < S) {
+      const float v = FIRST ? zk : zo + zk;
+      z[sh_unmirrored(m, base, i, j, k, K, sub)] = v * scale;
+    }
+    x = xn;
+    zo = zn;
+    s = sn;
+    i = in;
+    j = jn;
+    k = kn;
+  }
+}
+
 int seg_head_check(const char* what, int N, int64_t S, int K, int dtype) {
   PCRL_REQUIRE(N > 0 && S > 0 && S < ((int64_t)1 << 31) - 4096, "%s: bad sizes N=%d S=%lld", what, N, (long long)S);
   PCRL_REQUIRE(N <= 65535, "%s: at most 65535 samples per call, got %d", what, N);
@@ -407,6 +480,15 @@ void seg_head_launch_logits(dim3 grid, hipStream_t st, const void* a, const floa
   hipLaunchKernelGGL((seg_head_logits_kernel<T, K>), grid, dim3(SH_THREADS), 0, st, static_cast<const T*>(a), w, b, z, S);
 }
 
+template <typename T, int K>
+void seg_head_launch_logits_acc(bool first, dim3 grid, hipStream_t st, const void* a, const float* w, const float* b, float* z, int S, const ShMirror& m,
+                                float scale) {
+  if (first)
+    hipLaunchKernelGGL((seg_head_logits_acc_kernel<T, K, true>), grid, dim3(SH_THREADS), 0, st, static_cast<const T*>(a), w, b, z, S, m, scale);
+  else
+    hipLaunchKernelGGL((seg_head_logits_acc_kernel<T, K, false>), grid, dim3(SH_THREADS), 0, st, static_cast<const T*>(a), w, b, z, S, m, scale);
+}
+
 }  // namespace
 
 void pcrl_seg_sums_launch(const double* partial, int nb, int K, float wb, float wd, double* sums, float* loss, hipStream_t stream) {
@@ -424,6 +506,24 @@ extern "C" int pcrl_seg_head_logits(const void* a, const float* w, const float* 
   SH_DISPATCH_K(SH_LOGITS)
 #undef SH_LOGITS
   return pcrl_check_launch("seg_head_logits");
+}
+
+extern "C" int pcrl_seg_head_logits_acc(const void* a, const float* w, const float* b, float* z, int N, int64_t S, int K, int dtype, int cx, int cy, int cz,
+                                        int flip, int first, float scale, pcrl_stream_t stream) {
+  if (int rc = seg_head_check("seg_head_logits_acc", N, S, K, dtype)) return rc;
+  PCRL_REQUIRE(a && w && b && z, "seg_head_logits_acc: null pointer");
+  PCRL_REQUIRE(flip >= 0 && flip <= 7, "seg_head_logits_acc: flip %d is no mirror code (bit 0 = x, bit 1 = y, bit 2 = z: 0..7)", flip);
+  PCRL_REQUIRE(cx > 0 && cy > 0 && cz > 0 && (int64_t)cx * cy * cz == S, "seg_head_logits_acc: S = %lld voxels per sample against a grid of %d x %d x %d",
+               (long long)S, cx, cy, cz);
+  const dim3 grid(sh_gx(N, S), N);
+  const ShMirror m{cx, cy, cz, flip};
+  hipStream_t st = as_stream(stream);
+#define SH_LOGITS_ACC(KK)                                                                                                  \
+  if (dtype == PCRL_BF16) seg_head_launch_logits_acc<bf16, KK>(first != 0, grid, st, a, w, b, z, (int)S, m, scale);       \
+  else seg_head_launch_logits_acc<float, KK>(first != 0, grid, st, a, w, b, z, (int)S, m, scale)
+  SH_DISPATCH_K(SH_LOGITS_ACC)
+#undef SH_LOGITS_ACC
+  return pcrl_check_launch("seg_head_logits_acc");
 }
 
 extern "C" size_t pcrl_seg_head_ws_bytes(int N, int64_t S, int K) {

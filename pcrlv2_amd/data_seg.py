@@ -17,6 +17,8 @@ that cover it.  The tiled path above is what `--overlap 0` (the default) runs.
 Training-time augmentation (AugConfig, source_extent, cut_box, draw_aug_crop; CropLoader(aug=...)): the host draws rotation,
 zoom, flips and per-channel intensity parameters and cuts a source box around the crop; image channels and label bitmask are resampled together on
 the device (ops.seg_augment, csrc/seg_augment.hip) by train_seg.train_step.  Without `aug` nothing changes.
+
+Mirror test-time augmentation (parse_mirror, mirror_letters): the mirror codes train_seg.sliding_window shows every patch in.
 """
 from __future__ import annotations
 
@@ -183,6 +185,32 @@ def blend_weights(crop, window):
             i = np.arange(c, dtype=np.float64)
             out.append(np.exp(-0.5 * ((i - (c - 1) / 2.0) / (0.125 * c)) ** 2).astype(np.float32))
     return out
+
+
+# ---- mirror test-time augmentation --------------------------------------------------------------------------
+MIRROR_AXES = "xyz"          # a mirror code has bit 0 = x, bit 1 = y, bit 2 = z: the patch's first, second and third spatial axis
+
+
+def parse_mirror(text, flag="--mirror"):
+    """'none' (the default) -> [0]; 'all' -> [0..7]; a non-empty subset of the letters xyz in any order -> every combination of the chosen axes as
+    ascending mirror codes, the identity first ('xz' -> [0, 1, 4, 5]).  Anything else exits with its message."""
+    t = "none" if text is None else str(text).strip().lower()
+    if t == "none":
+        return [0]
+    letters = MIRROR_AXES if t == "all" else t
+    if not letters or any(c not in MIRROR_AXES for c in letters) or len(set(letters)) != len(letters):
+        raise SystemExit(f"{flag} {text}: none, all, or the axes to mirror along as distinct letters of xyz (xz: the four combinations of the x and z "
+                         "mirrors, the identity among them)")
+    chosen = sum(1 << MIRROR_AXES.index(c) for c in letters)
+    return [code for code in range(8) if code & ~chosen == 0]
+
+
+def mirror_letters(codes):
+    """The axes a list of mirror codes touches, as parse_mirror spells them: [0, 1, 4, 5] -> 'xz'; [0] -> 'none'."""
+    bits = 0
+    for code in codes:
+        bits |= int(code)
+    return "".join(c for i, c in enumerate(MIRROR_AXES) if bits >> i & 1) or "none"
 
 
 def cut_tile(case, start, own_from, crop):

@@ -636,11 +636,18 @@ class Segmenter3d(PCRLv23d):
         return ops.to_act(h, dt)
 
     @torch.no_grad()
-    def infer_logits(self, x, out=None):
+    def infer_logits(self, x, out=None, *, flip=0, accumulate=False, scale=1.0):
         """infer's forward followed by the head's logits alone (pcrl_seg_head_logits), whatever `self.training` says; nothing of the model is touched.
         -> float32 [N, D, H, W, K] (written into `out` when given): thresholding it at 0 is infer's mask, bit for bit.  What overlap-blended
-        sliding windows average (train_seg.sliding_window)."""
+        sliding windows average (train_seg.sliding_window).
+        With any of flip / accumulate / scale off its default the head is pcrl_seg_head_logits_acc and `out` is required: `x` is the ALREADY mirrored
+        patch and `flip` (bit 0 = D, bit 1 = H, bit 2 = W) names the mirroring to undo, so each logit lands on its un-mirrored voxel of `out`;
+        accumulate=False overwrites `out` (the first pass), True adds to what it holds; the result is multiplied by `scale` (float32)."""
         self._check(x, None)
         dt = self.compute_dtype
         fc = self.out_tr.final_conv
-        return ops.seg_head_logits(self._infer_features(x, dt), fc.weight, fc.bias, dt, out=out)
+        if flip == 0 and not accumulate and float(scale) == 1.0:
+            return ops.seg_head_logits(self._infer_features(x, dt), fc.weight, fc.bias, dt, out=out)
+        if out is None:
+            raise ValueError("Segmenter3d.infer_logits: flip / accumulate / scale write into the buffer `out`, which is required with them")
+        return ops.seg_head_logits_acc(self._infer_features(x, dt), fc.weight, fc.bias, dt, out, flip=flip, first=not accumulate, scale=scale)

@@ -1724,9 +1724,38 @@ def seg_head_logits(a, w, b, dtype, out=None):
     return out.view(N, D, H, W, K)
 
 
-def seg_cut_patches(img, starts, crop, out=None):
+def _mirror_code(flip, what):
+    try:
+        code = -1 if isinstance(flip, bool) else flip.__index__()
+    except AttributeError:
+        code = -1
+    if not 0 <= code <= 7:
+        raise PcrlError(f"{what}: flip {flip!r} is no mirror code (an integer 0..7: bit 0 = x, bit 1 = y, bit 2 = z)")
+    return code
+
+
+def seg_head_logits_acc(a, w, b, dtype, out, flip=0, first=False, scale=1.0):
+    """seg_head_logits of patches the network saw MIRRORED along the axes of `flip` (bit 0 = x, bit 1 = y, bit 2 = z of [N, D, H, W]), written into `out`
+    float32 [N, D, H, W, K] at the un-mirrored voxel (pcrl_seg_head_logits_acc): v = logit if first else out + logit; out = v * scale, plain float32.
+    Mirror test-time augmentation and checkpoint ensembles accumulate their passes with it in the one per-case buffer (train_seg.sliding_window)."""
+    N, S, K, wc, bc = _seg_args(a, w, b, None, dtype, "seg_head_logits_acc")
+    _, D, H, W, _ = dims(a)
+    flip = _mirror_code(flip, "seg_head_logits_acc")
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.numel() != N * S * K or not out.is_contiguous() or out.device != a.device:
+        raise PcrlError(f"seg_head_logits_acc: out must be a contiguous float32 tensor of {N * S * K} elements on {a.device} (it is read unless `first`), got "
+                        f"{getattr(out, 'dtype', type(out).__name__)} {tuple(getattr(out, 'shape', ()))}")
+    scale = float(scale)
+    if not scale == scale or scale in (float("inf"), float("-inf")):
+        raise PcrlError(f"seg_head_logits_acc: scale {scale} is not finite")
+    lib().call("pcrl_seg_head_logits_acc", a, wc, bc, out, N, S, K, dtype_code(dtype), D, H, W, flip, int(bool(first)), scale, stream_handle())
+    return out.view(N, D, H, W, K)
+
+
+def seg_cut_patches(img, starts, crop, out=None, flip=0):
     """The crop-sized patches of one case, cut on the device (pcrl_seg_cut_patches): img [C, X, Y, Z] float32 / float16, starts int32 [n, 3] on the same
-    device.  -> float32 [n, C, *crop], 0 outside the volume: data_seg.cut's image, byte for byte."""
+    device.  -> float32 [n, C, *crop], 0 outside the volume: data_seg.cut's image, byte for byte.  flip != 0 (a mirror code, bit 0 = x, bit 1 = y,
+    bit 2 = z): that box mirrored along those axes, zeros included (pcrl_seg_cut_patches_mirror); flip = 0 calls pcrl_seg_cut_patches."""
+    flip = _mirror_code(flip, "seg_cut_patches")
     if img.dim() != 4 or img.dtype not in (torch.float32, torch.float16) or not img.is_contiguous() or not img.is_cuda or img.numel() == 0:
         raise PcrlError(f"seg_cut_patches: the image must be a contiguous float32 / float16 [C, X, Y, Z] tensor on the GPU, got {img.dtype} {tuple(img.shape)} on {img.device}")
     if starts.dtype != torch.int32 or starts.dim() != 2 or starts.shape[1] != 3 or starts.shape[0] < 1 or not starts.is_contiguous() or starts.device != img.device:
@@ -1741,7 +1770,10 @@ def seg_cut_patches(img, starts, crop, out=None):
     elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != img.device or out.data_ptr() % 16:
         raise PcrlError(f"seg_cut_patches: out must be a contiguous float32 {shape} tensor on {img.device} at a 16-byte aligned address (the kernel "
                         f"stores 16 bytes at a time), got {out.dtype} {tuple(out.shape)} at offset {out.data_ptr() % 16}")
-    lib().call("pcrl_seg_cut_patches", img, int(img.dtype == torch.float16), starts, out, n, C, *img.shape[1:], *crop, stream_handle())
+    if flip == 0:
+        lib().call("pcrl_seg_cut_patches", img, int(img.dtype == torch.float16), starts, out, n, C, *img.shape[1:], *crop, stream_handle())
+    else:
+        lib().call("pcrl_seg_cut_patches_mirror", img, int(img.dtype == torch.float16), starts, out, n, C, *img.shape[1:], *crop, flip, stream_handle())
     return out
 
 

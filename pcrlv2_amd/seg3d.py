@@ -5,6 +5,8 @@
     python seg3d.py predict --data DIR --list test.txt --weights OUT/pcrlv2_seg3d_finetune_1.0_best.pt --out PRED
     python seg3d.py predict --data DIR --list test.txt --weights OUT/pcrlv2_seg3d_finetune_1.0_best.pt --out PRED --overlap 0.5 --window gaussian --probs
     python seg3d.py predict --data DIR --list test.txt --weights OUT/pcrlv2_seg3d_finetune_1.0_best.pt --out PRED --keep_largest all --min_voxels 8
+    python seg3d.py predict --data DIR --list test.txt --weights FOLD0/best.pt,FOLD1/best.pt --out PRED --overlap 0.5 --mirror all --probs
+    python seg3d.py train   --data DIR --phase finetune --weights PRETRAIN.pt --n_class 3 --in_channels 4 --val_overlap 0.5 --val_mirror xz --output OUT
     python seg3d.py postprocess --pred PRED --list DIR/test.txt --out CLEAN --n_class 3 --keep_largest 0,2 --min_voxels 8 --connectivity 26
     python seg3d.py score   --data DIR --list test.txt --pred PRED --n_class 3 --spacing 1,1,1 --csv scores.csv
 
@@ -19,7 +21,9 @@ DESIGN.md section 17).  `postprocess` cleans stored predictions by their connect
 components below N voxels; `predict` takes the same three options and cleans a mask on the device before it is written (csrc/components.hip,
 DESIGN.md section 18).  Without them `predict` writes what it always wrote.  `train --augment` (or any `--aug_*` option) resamples the training
 crops on the device -- rotation, zoom and flips of image channels and label bitmask in one kernel, then gain, bias, gamma and noise per channel
-(csrc/seg_augment.hip); without those options training does what it always did.
+(csrc/seg_augment.hip); without those options training does what it always did.  `predict --mirror` / `train --val_mirror` show
+every patch mirrored along each combination of the named axes as well, and `predict --weights a.pt,b.pt` runs several checkpoints: the un-mirrored
+logits of all passes are averaged in the sliding window's one per-case buffer before the blend; `none` and one file are the earlier paths, unchanged.
 
     python seg3d.py prepare --data RAW --manifest cases.tsv --save DIR --regions "1,2,4;1,4;4" --spacing 1,1,1 --split 0.7,0.1,0.2 --seed 0
     python seg3d.py restore --prep DIR --pred PRED --list DIR/test.txt --out ORIG --paint "2,1,4" --nifti
@@ -46,9 +50,10 @@ def check_train(args):
         raise SystemExit("--phase scratch starts from random weights: drop --weights or use --phase finetune")
     if args.b < 1 or args.epochs < 1 or args.steps_per_epoch < 0:
         raise SystemExit("--b and --epochs must be positive, --steps_per_epoch non-negative")
-    from .data_seg import check_overlap, check_window, parse_aug
+    from .data_seg import check_overlap, check_window, parse_aug, parse_mirror
     check_overlap(args.val_overlap, "--val_overlap")
     check_window(args.val_window, "--val_window")
+    parse_mirror(args.val_mirror, "--val_mirror")
     parse_aug(args)
 
 
@@ -62,14 +67,16 @@ def train(args):
 
 def check_predict(args):
     """Every refused combination exits with its message, before anything touches a GPU."""
-    from .data_seg import check_overlap, check_window, parse_crop
+    from .data_seg import check_overlap, check_window, parse_crop, parse_mirror
+    from .train_seg import split_weights
     parse_crop(args.crop)
     if args.b < 1:
         raise SystemExit("--b must be positive")
     check_window(args.window)
-    if check_overlap(args.overlap) == 0 and args.probs:
-        raise SystemExit("--probs writes the blended probabilities of overlapping windows: it needs --overlap > 0 (the tiled path thresholds its logits "
-                         "inside the kernel)")
+    sliding = len(parse_mirror(args.mirror)) > 1 or len(split_weights(args.weights)) > 1      # these keep per-patch logits also at --overlap 0
+    if check_overlap(args.overlap) == 0 and args.probs and not sliding:
+        raise SystemExit("--probs writes the blended probabilities of overlapping windows: it needs --overlap > 0, a --mirror other than none or several "
+                         "--weights (the tiled path thresholds its logits inside the kernel)")
 
 
 def predict(args):
@@ -138,6 +145,8 @@ def build_parser():
     tr.add_argument("--val_overlap", type=float, default=0.0, help="validation and the final test by sliding windows that overlap by this fraction of "
                     "the crop, blended (0..0.75); 0 = stride-tiled patches")
     tr.add_argument("--val_window", default="gaussian", help="blending window with --val_overlap > 0: gaussian | constant")
+    tr.add_argument("--val_mirror", default="none", help="mirror test-time augmentation of validation and the final test: none | all | a subset of the "
+                    "letters xyz; with --val_overlap 0 the sliding windows run with the constant window")
     tr.add_argument("--augment", action="store_true", help="resample the training crops on the device: rotation, zoom, gain, bias, gamma and noise at "
                     "the defaults of the --aug_* options; each of those implies it")
     tr.add_argument("--aug_rotate", default=None, help="largest rotation about each axis in degrees, 0..45 (15)")
@@ -152,7 +161,7 @@ def build_parser():
     pr = sub.add_parser("predict", help="write <case>_pred.npy (uint8 bitmask) for every case of a list")
     pr.add_argument("--data", required=True, help="directory with <case>_img.npy")
     pr.add_argument("--list", required=True, help="file of case names (in --data, or a path)")
-    pr.add_argument("--weights", required=True, help="a checkpoint of `train`")
+    pr.add_argument("--weights", required=True, help="a checkpoint of `train`, or several separated by commas: their logits are averaged")
     pr.add_argument("--out", required=True, help="output directory")
     pr.add_argument("--crop", default="64,64,32", help="the crop the segmenter was trained on")
     pr.add_argument("--b", type=int, default=8, help="patches per forward")
@@ -161,7 +170,10 @@ def build_parser():
     pr.add_argument("--overlap", type=float, default=0.0, help="sliding windows that overlap by this fraction of the crop, blended (0..0.75); 0 = "
                     "stride-tiled patches, every voxel from one patch")
     pr.add_argument("--window", default="gaussian", help="blending window with --overlap > 0: gaussian | constant")
-    pr.add_argument("--probs", action="store_true", help="with --overlap > 0: also write <case>_prob.npy, float16 [K, X, Y, Z]")
+    pr.add_argument("--probs", action="store_true", help="with --overlap > 0, a --mirror or several --weights: also write <case>_prob.npy, float16 "
+                    "[K, X, Y, Z]")
+    pr.add_argument("--mirror", default="none", help="mirror test-time augmentation: none | all | a subset of the letters xyz; every patch is also shown "
+                    "mirrored along each combination of these axes and the un-mirrored logits are averaged")
     _cleanup_options(pr)
     pp = sub.add_parser("postprocess", help="connected-component clean-up of stored <case>_pred.npy into another directory")
     pp.add_argument("--pred", required=True, help="directory with <case>_pred.npy (the --out of `predict`)")

@@ -21,6 +21,10 @@ classes on the device (csrc/components.hip): all but the largest, and / or those
 `seg3d.py train --augment` (augment_batch): the loader hands over source boxes and drawn parameters, and the step's forward
 resamples image channels and label bitmask together on the device (csrc/seg_augment.hip), then adds noise and gamma (csrc/augment.hip).  Evaluation,
 prediction and the sliding window never see it.
+
+`predict --mirror` / `--weights a.pt,b.pt` and `train --val_mirror` (sliding_window(mirror=, models=)): every patch batch is also
+shown mirrored and to every checkpoint, and the un-mirrored logits of all passes are averaged in the sliding window's one per-case buffer
+(csrc/seg_head.hip's accumulating logits kernel, csrc/seg_blend.hip's mirrored cutter).  At `none` and one checkpoint nothing changes.
 """
 from __future__ import print_function
 
@@ -128,13 +132,29 @@ def _fmt(val):
 
 
 # ---- overlap-blended sliding windows ----------------------------------------------------------------------------------------------
-def sliding_window(model, case, crop, b, overlap, window, *, counts=None, row=0, want_mask=True, want_probs=False, max_bytes=16 << 30):
+def sliding_window(model, case, crop, b, overlap, window, *, counts=None, row=0, want_mask=True, want_probs=False, max_bytes=16 << 30, mirror=(0,),
+                   models=None):
     """One case by overlapping crop-sized windows (data_seg.windows) whose logits are blended with a centre-weighted window (data_seg.blend_weights):
     the image (and the labels, when the case has them) is uploaded once, `b` patches per forward are cut on the device (ops.seg_cut_patches),
     model.infer_logits writes into the per-case buffer [P, *crop, K], and ONE ops.seg_blend call turns it into the prediction; with labels, row `row`
     of `counts` gets {TP, |pred|, |gt|} added.  -> (mask uint8 [X, Y, Z] | None, probs float32 [K, X, Y, Z] | None, sums float64 [4 K + 1]), on the
-    device; an unlabelled case without `counts` has nothing to sum: its sums are None and the blend runs without them.  A buffer above `max_bytes` is refused before anything is uploaded."""
+    device; an unlabelled case without `counts` has nothing to sum: its sums are None and the blend runs without them.  A buffer above `max_bytes` is refused before anything is uploaded.
+
+    Mirror test-time augmentation and checkpoint ensembles.  `mirror`: mirror codes (data_seg.parse_mirror; bit 0 = x, bit 1 = y,
+    bit 2 = z); `models`: a list that replaces `model` as the source of logits (`model` stays the source of n_class, wb and wd).  Per batch of patches,
+    for each model in list order and each code in ascending order, the patches are cut mirrored (ops.seg_cut_patches(flip=code)) and
+    infer_logits(flip=code) adds their logits, un-mirrored, into the SAME slice of the per-case buffer, which keeps its size; the first pass overwrites,
+    the last multiplies by float32(1 / (E M)) (E models, M codes).  What the blend then averages is the mean of the LOGITS over the passes (not of the
+    probabilities), formed in float32 in pass order: the blend is linear in the logits, so this equals averaging blended logits.  With one model and
+    mirror (0,) the calls are exactly those without the two arguments."""
     crop, K, b = tuple(int(c) for c in crop), int(model.n_class), int(b)
+    nets = [model] if models is None else list(models)
+    codes = sorted({int(c) for c in mirror})
+    if not nets or not codes or codes[0] < 0 or codes[-1] > 7:
+        raise ValueError(f"sliding_window: mirror codes are integers 0..7 and `models` is not empty, got mirror {tuple(mirror)} and {len(nets)} models")
+    if models is not None and any(int(net.n_class) != K for net in nets):
+        raise ValueError(f"sliding_window: every model of `models` must have the {K} classes of `model`, got {[int(net.n_class) for net in nets]}")
+    passes = [(net, code) for net in nets for code in codes]
     axes = _data.windows(case.shape, crop, overlap)
     weights = _data.blend_weights(crop, window)
     starts = _data.window_starts(axes)
@@ -143,13 +163,16 @@ def sliding_window(model, case, crop, b, overlap, window, *, counts=None, row=0,
     if nbytes > max_bytes:
         raise SystemExit(f"{case.name}: the logits of its {P} patches at overlap {overlap:g} need {nbytes / 2 ** 30:.1f} GiB, above the limit of "
                          f"{max_bytes / 2 ** 30:.1f} GiB for one case: use a smaller --overlap")
-    dev = next(model.parameters()).device
+    dev = next(nets[0].parameters()).device
     img = torch.from_numpy(np.ascontiguousarray(case.img)).to(dev)
     labels = None if case.seg is None else torch.from_numpy(np.ascontiguousarray(case.seg)).to(dev)
     st = torch.tensor(starts, dtype=torch.int32, device=dev)
     z = torch.empty((P,) + crop + (K,), dtype=torch.float32, device=dev)
     for a in range(0, P, b):
-        model.infer_logits(_ops.seg_cut_patches(img, st[a:a + b], crop), out=z[a:a + b])
+        for i, (net, code) in enumerate(passes):       # one pass of code 0: flip=0, overwrite, scale 1 -- the plain cutter and the plain logits kernel
+            last = i == len(passes) - 1
+            net.infer_logits(_ops.seg_cut_patches(img, st[a:a + b], crop, flip=code), out=z[a:a + b], flip=code, accumulate=i > 0,
+                             scale=np.float32(1.0 / len(passes)) if last else 1.0)
     mask, probs, sums, _, _ = _ops.seg_blend(z, [torch.tensor(a, dtype=torch.int32, device=dev) for a in axes], [torch.from_numpy(w).to(dev) for w in weights],
                                              case.shape, labels=labels, counts=counts, row=row, want_mask=want_mask, want_probs=want_probs,
                                              want_sums=labels is not None or counts is not None, wb=model.wb, wd=model.wd)
@@ -167,9 +190,10 @@ class _CaseShard:
         return iter(self.mine)
 
 
-def evaluate_sliding(model, cases, crop, b, overlap, window, rank=0, world=1, group=None):
+def evaluate_sliding(model, cases, crop, b, overlap, window, rank=0, world=1, group=None, mirror=(0,)):
     """`evaluate` with every case predicted by sliding_window: the same dictionary from the same ONE held_out_pass, one all_reduce of sums and counts
-    and one host read-back.  The sums of the cases add up (they are sums over counted voxels), so the loss is the pass's, as in `evaluate`."""
+    and one host read-back.  The sums of the cases add up (they are sums over counted voxels), so the loss is the pass's, as in `evaluate`.
+    `mirror`: sliding_window's mirror codes."""
     dev = next(model.parameters()).device
     K, n_cases = model.n_class, len(cases)
     ns = 4 * K + 1
@@ -177,7 +201,7 @@ def evaluate_sliding(model, cases, crop, b, overlap, window, rank=0, world=1, gr
     acc = torch.zeros(ns + n_cases * K * 3, dtype=torch.float64, device=dev)
 
     def per_case(ci):
-        acc[:ns] += sliding_window(model, cases[ci], crop, b, overlap, window, counts=counts, row=ci, want_mask=False)[2]
+        acc[:ns] += sliding_window(model, cases[ci], crop, b, overlap, window, counts=counts, row=ci, want_mask=False, mirror=mirror)[2]
 
     def counts_into_acc():
         acc[ns:] = counts[:n_cases].reshape(-1).double()
@@ -207,7 +231,12 @@ def _train_segmenter(args, distributed):
     loaders = _data.loaders(args, rank, world)
     overlap, window = float(getattr(args, "val_overlap", 0.0)), getattr(args, "val_window", "gaussian")
     crop = _data.parse_crop(args.crop)
-    if overlap > 0:          # validation and the final test by overlap-blended sliding windows; 0 (the default): the tiled pass
+    mirror = _data.parse_mirror(getattr(args, "val_mirror", None), "--val_mirror")
+    if len(mirror) > 1:      # mirrored validation and test: sliding windows also at --val_overlap 0, there with the constant window (one patch per voxel)
+        window = window if overlap > 0 else "constant"
+        held_out = lambda model, loader: evaluate_sliding(model, loader.cases, crop, args.b, overlap, window, rank, world, mirror=mirror)      # noqa: E731
+        tail = "\toverlap {0:g} {1}\tmirror {2}".format(overlap, window, _data.mirror_letters(mirror))
+    elif overlap > 0:        # validation and the final test by overlap-blended sliding windows; 0 (the default): the tiled pass
         held_out = lambda model, loader: evaluate_sliding(model, loader.cases, crop, args.b, overlap, window, rank, world)      # noqa: E731
         tail = "\toverlap {0:g} {1}".format(overlap, window)
     else:
@@ -246,11 +275,41 @@ def _train_segmenter(args, distributed):
 
 
 # ---- predict ----------------------------------------------------------------------------------------------------------------------
-def load_segmenter(weights, device, amp=False):
+def split_weights(text):
+    """--weights of `predict`: one checkpoint, or several separated by commas (an ensemble) -> the list of paths; an empty entry exits with its message."""
+    files = [f.strip() for f in str(text).split(",")]
+    if not files or any(not f for f in files):
+        raise SystemExit(f"--weights {text}: one checkpoint of `seg3d.py train`, or several separated by commas (their logits are averaged)")
+    return files
+
+
+def read_state_dict(weights):
     if not os.path.isfile(weights):
         raise SystemExit(f"--weights {weights}: no such file (a checkpoint written by `seg3d.py train`)")
-    sd = torch.load(weights, map_location="cpu", weights_only=False)["state_dict"]
-    model = Segmenter3d(sd["out_tr.final_conv.weight"].shape[0], in_channels=sd["down_tr64.ops.0.conv1.weight"].shape[1])
+    return torch.load(weights, map_location="cpu", weights_only=False)["state_dict"]
+
+
+def state_dict_sizes(sd):
+    """(n_class, in_channels) of a segmenter's state dict."""
+    return int(sd["out_tr.final_conv.weight"].shape[0]), int(sd["down_tr64.ops.0.conv1.weight"].shape[1])
+
+
+def check_ensemble(files, state_dicts):
+    """The checkpoints of an ensemble agree in n_class and in_channels, or the first one that differs from the first exits with a message naming both
+    files.  On the host, on the state dicts.  -> (n_class, in_channels)"""
+    first = state_dict_sizes(state_dicts[0])
+    for f, sd in zip(files[1:], state_dicts[1:]):
+        got = state_dict_sizes(sd)
+        if got != first:
+            raise SystemExit(f"--weights: {f} has n_class {got[0]} and in_channels {got[1]}, {files[0]} has n_class {first[0]} and in_channels {first[1]}: "
+                             "the checkpoints of an ensemble must agree in both (their logits are averaged voxel by voxel)")
+    return first
+
+
+def load_segmenter(weights, device, amp=False, state_dict=None):
+    sd = read_state_dict(weights) if state_dict is None else state_dict
+    n_class, in_channels = state_dict_sizes(sd)
+    model = Segmenter3d(n_class, in_channels=in_channels)
     model.load_state_dict(sd)
     model = model.to(device)
     if amp:
@@ -275,9 +334,18 @@ def predict(args, log=print):
     crop = _data.parse_crop(args.crop)
     overlap, window, want_probs = float(getattr(args, "overlap", 0.0)), getattr(args, "window", "gaussian"), bool(getattr(args, "probs", False))
     rules = parse_cleanup(args)          # None (the default): the masks are written as predicted
+    mirror = _data.parse_mirror(getattr(args, "mirror", None))
+    files = split_weights(args.weights)
+    state_dicts = [read_state_dict(f) for f in files]
+    check_ensemble(files, state_dicts)       # on the host, before any model goes to the device
+    # mirrored passes and ensembles add logits into sliding_window's buffer: they take that path also at --overlap 0, where every voxel has one patch
+    # and the mask does not depend on the (positive) window
+    sliding = overlap > 0 or len(mirror) > 1 or len(files) > 1
     device = torch.device("cuda", args.gpu)
     torch.cuda.set_device(device)
-    model = load_segmenter(args.weights, device, args.amp)
+    models = [load_segmenter(f, device, args.amp, state_dict=sd) for f, sd in zip(files, state_dicts)]
+    model = models[0]
+    del state_dicts
     if rules is not None:
         rules = (resolve_keep(rules[0], model.n_class),) + rules[1:]
     os.makedirs(args.out, exist_ok=True)
@@ -285,8 +353,8 @@ def predict(args, log=print):
     for name in names:
         case = _data.open_case(args.data, name, model.n_class, model.in_channels, need_seg=False)
         case.seg = None          # the prediction does not look at labels
-        if overlap > 0:
-            mask, probs, _ = sliding_window(model, case, crop, args.b, overlap, window, want_probs=want_probs)
+        if sliding:
+            mask, probs, _ = sliding_window(model, case, crop, args.b, overlap, window, want_probs=want_probs, mirror=mirror, models=models)
             if rules is not None:
                 mask = postprocess_mask(mask, model.n_class, *rules)[0]
             np.save(os.path.join(args.out, name + "_pred.npy"), mask.cpu().numpy())
