@@ -198,6 +198,11 @@ def stream_handle() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def call_on_stream(name: str, *args):
+    """lib().call with torch's current stream as the last argument: the data-side modules' launches (the per-step operators pass stream_handle() themselves)."""
+    return lib().call(name, *args, stream_handle())
+
+
 def dtype_code(dt: torch.dtype) -> int:
     if dt == torch.float32:
         return PCRL_F32

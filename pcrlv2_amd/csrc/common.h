@@ -41,6 +41,17 @@ int pcrl_check_launch(const char* what);
 
 static inline hipStream_t as_stream(pcrl_stream_t s) { return (hipStream_t)s; }
 
+// Blocks of `threads` for a grid-stride loop over `items`: min(max(ceil(items / threads), 1), cap).
+inline int capped_blocks(int64_t items, int threads, int64_t cap) {
+  const int64_t want = (items + threads - 1) / threads;
+  return (int)(want < 1 ? 1 : want < cap ? want : cap);
+}
+// Do the byte ranges [a, a + na) and [b, b + nb) overlap?  A null pointer overlaps nothing.
+inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  return a && b && pa < pb + nb && pb < pa + na;
+}
+
 // ---- element type helpers ---------------------------------------------------------------
 __device__ __forceinline__ float to_f(float v) { return v; }
 __device__ __forceinline__ float to_f(bf16 v) { return (float)v; }
@@ -95,6 +106,38 @@ __device__ __forceinline__ float wave_sum(float v) {
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// the integer ones are exact: counts, boxes and scores are the same bytes whatever the order
+__device__ __forceinline__ unsigned wave_sum(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int w = __shfl_xor(v, o, 64);
+    v = w < v ? w : v;
+  }
+  return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int w = __shfl_xor(v, o, 64);
+    v = w > v ? w : v;
+  }
   return v;
 }
 // Sum over a 256-thread block; result valid in thread 0.  `red` = 4 values of LDS scratch.

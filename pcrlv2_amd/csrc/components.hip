@@ -179,12 +179,6 @@ __global__ void __launch_bounds__(CCL_THREADS) ccl_merge_kernel(int* __restrict_
       }
 }
 
-__device__ __forceinline__ int ccl_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // inclusive scan over the 64 lanes
 __device__ __forceinline__ int ccl_wave_scan(int v, int lane) {
 #pragma unroll
@@ -222,7 +216,7 @@ __global__ void __launch_bounds__(CCL_THREADS) ccl_flatten_kernel(const int* __r
     }
     R[v] = r;
   }
-  roots = ccl_wave_sum(roots);
+  roots = wave_sum(roots);
   if ((t & 63) == 0) red[t >> 6] = roots;
   __syncthreads();
   if (t == 0) bsum[blockIdx.x] = red[0] + red[1] + red[2] + red[3];

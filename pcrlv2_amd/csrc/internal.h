@@ -125,3 +125,16 @@ int pcrl_weighted_colsum(const void* v, const float* rowscale, float* out, void*
 // partial [nb][32] float64 per-block sums (slot k * 4 + {I, P, G, BCE}, slot 28: counted voxels) -> sums [4 K + 1] and loss [1], added in block order
 constexpr int PCRL_SEG_SLOTS = 32, PCRL_SEG_CNT_SLOT = 28;
 void pcrl_seg_sums_launch(const double* partial, int nb, int K, float wb, float wd, double* sums, float* loss, hipStream_t stream);
+// The probability of a logit: the blend's loss equals the head's only because both use this one expression.
+__device__ __forceinline__ float seg_sigmoid(float z) { return 1.0f / (1.0f + expf(-z)); }
+// CALL(KK) with the compile-time class count KK = K; the entry points have checked 1 <= K <= 7.
+#define PCRL_SEG_DISPATCH_K(CALL)            \
+  switch (K) {                               \
+    case 1: CALL(1); break;                  \
+    case 2: CALL(2); break;                  \
+    case 3: CALL(3); break;                  \
+    case 4: CALL(4); break;                  \
+    case 5: CALL(5); break;                  \
+    case 6: CALL(6); break;                  \
+    default: CALL(7); break;                 \
+  }

@@ -40,19 +40,6 @@ __device__ __forceinline__ int mirror(int i, int n) {     // scipy.ndimage mode 
   return i >= n ? p - i : i;
 }
 
-__device__ __forceinline__ int wave_min(int v) {
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ int wave_add(int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // ---- ITK linear resample to 1 mm ----
 __device__ __forceinline__ void lerp_axis(int o, int n, double spacing, bool& inside, int& f0, int& f1, double& t) {
   const double ci = ((double)o * 1.0) / spacing;
@@ -226,14 +213,9 @@ __global__ void __launch_bounds__(256) zoom_kernel(const int64_t* __restrict__ r
     }
   }
   if (D > 0) {
-    score = wave_add(score);
+    score = wave_sum(score);
     if ((threadIdx.x & 63) == 0 && score != 0) atomicAdd(&stats[3 * w], score);
   }
-}
-
-inline unsigned grid_for(int64_t work, unsigned cap) {
-  const int64_t g = (work + 255) / 256;
-  return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
 }
 
 }  // namespace
@@ -244,7 +226,7 @@ extern "C" int pcrl_prep_resample(const int16_t* in, int16_t* out, int X, int Y,
   PCRL_REQUIRE(X > 0 && Y > 0 && Z > 0 && OX > 0 && OY > 0 && OZ > 0, "prep_resample: bad shape");
   PCRL_REQUIRE(spacing_x > 0.0 && spacing_y > 0.0 && spacing_z > 0.0, "prep_resample: spacing must be positive");
   const int64_t total = (int64_t)OX * OY * OZ;
-  hipLaunchKernelGGL(resample_kernel, dim3(grid_for(total, 8192)), dim3(256), 0, as_stream(stream), in, out, X, Y, Z, OX, OY, OZ, spacing_x,
+  hipLaunchKernelGGL(resample_kernel, dim3(capped_blocks(total, 256, 8192)), dim3(256), 0, as_stream(stream), in, out, X, Y, Z, OX, OY, OZ, spacing_x,
                      spacing_y, spacing_z);
   return pcrl_check_launch("prep_resample");
 }
@@ -256,11 +238,11 @@ extern "C" int pcrl_prep_windows(const int16_t* vol, int X, int Y, int Z, const 
   PCRL_REQUIRE(max_src > 0 && max_cols > 0 && out_len > 0 && ws_len > 0, "prep_windows: bad sizes");
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(init_stats_kernel, dim3((W + 255) / 256), dim3(256), 0, s, stats, W);
-  const unsigned gs = grid_for(max_src, 1024);
+  const unsigned gs = capped_blocks(max_src, 256, 1024);
   hipLaunchKernelGGL(norm_kernel, dim3(gs, W), dim3(256), 0, s, vol, X, Y, Z, rec, stats, ws, ws_len);
   hipLaunchKernelGGL(filter_kernel<0>, dim3(gs, W), dim3(256), 0, s, rec, prm, ws, ws_len);
   hipLaunchKernelGGL(filter_kernel<1>, dim3(gs, W), dim3(256), 0, s, rec, prm, ws, ws_len);
   hipLaunchKernelGGL(filter_kernel<2>, dim3(gs, W), dim3(256), 0, s, rec, prm, ws, ws_len);
-  hipLaunchKernelGGL(zoom_kernel, dim3(grid_for(max_cols, 65535), W), dim3(256), 0, s, rec, prm, ws, ws_len, out, out_len, stats);
+  hipLaunchKernelGGL(zoom_kernel, dim3(capped_blocks(max_cols, 256, 65535), W), dim3(256), 0, s, rec, prm, ws, ws_len, out, out_len, stats);
   return pcrl_check_launch("prep_windows");
 }

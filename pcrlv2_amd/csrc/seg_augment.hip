@@ -77,11 +77,6 @@ __global__ void __launch_bounds__(SA_THREADS) seg_aug_kernel(const T* __restrict
   lab[(int64_t)b * V + i] = in ? src_lab[(int64_t)b * SV + (nx * g.Sy + ny) * g.Sz + nz] : (uint8_t)0x80;
 }
 
-inline bool sa_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a0 < b0 + (uintptr_t)nb && b0 < a0 + (uintptr_t)na;
-}
-
 }  // namespace
 
 extern "C" int pcrl_seg_aug_resample(const void* src, int src_half, const uint8_t* src_lab, float* y, uint8_t* lab, const float* inv, const float* gain,
@@ -94,8 +89,8 @@ extern "C" int pcrl_seg_aug_resample(const void* src, int src_half, const uint8_
   const int64_t SV = (int64_t)Sx * Sy * Sz, V = (int64_t)X * Y * Z, lim = (int64_t)1 << 31;
   PCRL_REQUIRE(SV < lim && V < lim, "seg_aug_resample: a source box or a crop of 2^31 voxels or more (voxel indices are 32-bit)");
   const int64_t src_bytes = (int64_t)B * C * SV * (src_half ? 2 : 4), y_bytes = (int64_t)B * C * V * 4;
-  PCRL_REQUIRE(!sa_overlap(y, y_bytes, src, src_bytes) && !sa_overlap(y, y_bytes, src_lab, B * SV) && !sa_overlap(lab, B * V, src, src_bytes) &&
-                   !sa_overlap(lab, B * V, src_lab, B * SV) && !sa_overlap(y, y_bytes, lab, B * V),
+  PCRL_REQUIRE(!ranges_overlap(y, y_bytes, src, src_bytes) && !ranges_overlap(y, y_bytes, src_lab, B * SV) && !ranges_overlap(lab, B * V, src, src_bytes) &&
+                   !ranges_overlap(lab, B * V, src_lab, B * SV) && !ranges_overlap(y, y_bytes, lab, B * V),
                "seg_aug_resample: the outputs overlap the sources or each other (a gather cannot run in place)");
   const SaGeom g{C, Sx, Sy, Sz, X, Y, Z};
   const dim3 grid((unsigned)((V + SA_THREADS - 1) / SA_THREADS), (unsigned)B);

@@ -19,7 +19,7 @@
 //           once per instruction -- conflict-free.  There is no LDS traffic inside the voxel loop.
 // cut       a pure copy: thread = 4 consecutive z of one (patch, channel, x, y) row; four scalar loads (the source run starts at any z), one 16-byte
 //           store; what lies outside the volume is 0, and float16 sources are widened exactly.
-// mirror    the cutter's sibling for mirror test-time augmentation (seg_cut_patches_mirror; flip bit 0 = x, bit 1 = y, bit 2 = z): the same thread ->
+// mirror    the cutter's MIRROR instantiation for mirror test-time augmentation (seg_cut_patches_mirror; flip bit 0 = x, bit 1 = y, bit 2 = z): the same thread ->
 //           output mapping and the same 16-byte store; the patch BOX is mirrored, its zeros outside the volume included.  An x / y mirror moves
 //           whole source rows; with a z mirror a thread's four scalar loads run backwards, and the 64 threads of a wave still read one contiguous
 //           span of source rows (the same cache lines, in reverse).
@@ -33,8 +33,6 @@ struct SbGeom {
   int X, Y, Z, cx, cy, cz, nx, ny, nz;
 };
 
-__device__ __forceinline__ float sb_sigmoid(float z) { return 1.0f / (1.0f + expf(-z)); }      // sh_sigmoid's expression
-
 // first index i of the ascending list s[0..n) with s[i] > t (n: none)
 __device__ __forceinline__ int sb_first_above(const int* __restrict__ s, int n, int t) {
   int lo = 0, hi = n;
@@ -46,18 +44,7 @@ __device__ __forceinline__ int sb_first_above(const int* __restrict__ s, int n, 
   return lo;
 }
 
-__device__ __forceinline__ unsigned sb_wave_sum(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
-  return v;
-}
-
-inline int sb_blocks(int64_t V) {
-  const int64_t want = (V + SB_THREADS - 1) / SB_THREADS;
-  return (int)(want < SB_MAX_BLOCKS ? want : SB_MAX_BLOCKS);
-}
-
-// grid = sb_blocks(V); block = 256.  partial[block][32] float64 (seg_head.hip's slots) with STATS.
+// grid = capped_blocks(V, 256, SB_MAX_BLOCKS); block = 256.  partial[block][32] float64 (seg_head.hip's slots) with STATS.
 template <int K, bool STATS>
 __global__ void __launch_bounds__(SB_THREADS) seg_blend_kernel(const float* __restrict__ z, const int* __restrict__ sx, const int* __restrict__ sy,
                                                               const int* __restrict__ sz, const float* __restrict__ wx, const float* __restrict__ wy,
@@ -115,7 +102,7 @@ __global__ void __launch_bounds__(SB_THREADS) seg_blend_kernel(const float* __re
         numden[(int64_t)(K + 1 + c) * V + v] = num[c] / den;
       }
       if (probs || STATS) {
-        const float zb = num[c] / den, p = sb_sigmoid(zb);
+        const float zb = num[c] / den, p = seg_sigmoid(zb);
         if (probs) probs[(int64_t)c * V + v] = p;
         if (STATS && counted) {
           const bool gt = (lab >> c) & 1u;
@@ -138,7 +125,7 @@ __global__ void __launch_bounds__(SB_THREADS) seg_blend_kernel(const float* __re
 #pragma unroll
   for (int c = 0; c < K; ++c) {
     const double a = wave_sum(sI[c]), b = wave_sum(sP[c]), d = wave_sum(sG[c]), e = wave_sum(sB[c]);
-    const unsigned p = sb_wave_sum(cTP[c]), q = sb_wave_sum(cPr[c]), r = sb_wave_sum(cGt[c]);
+    const unsigned p = wave_sum(cTP[c]), q = wave_sum(cPr[c]), r = wave_sum(cGt[c]);
     if (lane == 0) {
       red[wid][c * 4 + 0] = a;
       red[wid][c * 4 + 1] = b;
@@ -149,7 +136,7 @@ __global__ void __launch_bounds__(SB_THREADS) seg_blend_kernel(const float* __re
       redc[wid][c * 3 + 2] = r;
     }
   }
-  cnt = sb_wave_sum(cnt);
+  cnt = wave_sum(cnt);
   if (lane == 0) red[wid][PCRL_SEG_CNT_SLOT] = (double)cnt;
   __syncthreads();
   if (t < 4 * K || t == PCRL_SEG_CNT_SLOT) partial[(int64_t)blockIdx.x * PCRL_SEG_SLOTS + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
@@ -167,10 +154,12 @@ void seg_blend_launch(bool stats, int nb, hipStream_t st, const float* z, const 
                        nullptr);
 }
 
-// grid = ceil(total / 256) with total = n * C * cx * cy * (cz / 4); block = 256.
-template <typename T>
+// grid = ceil(total / 256) with total = n * C * cx * cy * (cz / 4); block = 256.  MIRROR: output voxel (i, j, k) of a patch is voxel (fx ? cx-1-i : i,
+// fy ? cy-1-j : j, fz ? cz-1-k : k) of the patch BOX, zeros outside the volume included -- the same grid and the same thread -> output mapping; with a
+// z-mirror the four scalar loads of a thread run backwards.  Without MIRROR `flip` is not read.
+template <typename T, bool MIRROR>
 __global__ void __launch_bounds__(SB_THREADS) seg_cut_kernel(const T* __restrict__ img, const int* __restrict__ starts, float* __restrict__ out, int64_t total,
-                                                            int C, int X, int Y, int Z, int cx, int cy, int cz) {
+                                                            int C, int X, int Y, int Z, int cx, int cy, int cz, int flip) {
   const int64_t q = (int64_t)blockIdx.x * SB_THREADS + threadIdx.x;
   if (q >= total) return;
   const int cz4 = cz >> 2;
@@ -182,37 +171,8 @@ __global__ void __launch_bounds__(SB_THREADS) seg_cut_kernel(const T* __restrict
   r /= cx;
   const int c = (int)(r % C);
   const int64_t p = r / C;
-  const int64_t x = (int64_t)starts[p * 3] + i, y = (int64_t)starts[p * 3 + 1] + j, z0 = (int64_t)starts[p * 3 + 2] + 4 * k4;
-  const bool row_in = x >= 0 && x < X && y >= 0 && y < Y;
-  const T* __restrict__ src = img + (((int64_t)c * X + (row_in ? x : 0)) * Y + (row_in ? y : 0)) * Z;
-  float4 o;
-  float* ov = reinterpret_cast<float*>(&o);
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int64_t zz = z0 + u;
-    ov[u] = (row_in && zz >= 0 && zz < Z) ? (float)src[zz] : 0.0f;
-  }
-  *reinterpret_cast<float4*>(out + q * 4) = o;
-}
-
-// The cutter's mirrored sibling, same grid and same thread -> output mapping: output voxel (i, j, k) of a patch is voxel (fx ? cx-1-i : i,
-// fy ? cy-1-j : j, fz ? cz-1-k : k) of the patch BOX, zeros outside the volume included.  With a z-mirror the four scalar loads of a thread run backwards.
-template <typename T>
-__global__ void __launch_bounds__(SB_THREADS) seg_cut_mirror_kernel(const T* __restrict__ img, const int* __restrict__ starts, float* __restrict__ out,
-                                                                   int64_t total, int C, int X, int Y, int Z, int cx, int cy, int cz, int flip) {
-  const int64_t q = (int64_t)blockIdx.x * SB_THREADS + threadIdx.x;
-  if (q >= total) return;
-  const int cz4 = cz >> 2;
-  const int k4 = (int)(q % cz4);
-  int64_t r = q / cz4;
-  const int j = (int)(r % cy);
-  r /= cy;
-  const int i = (int)(r % cx);
-  r /= cx;
-  const int c = (int)(r % C);
-  const int64_t p = r / C;
-  const int pi = (flip & 1) ? cx - 1 - i : i, pj = (flip & 2) ? cy - 1 - j : j;
-  const int pk0 = (flip & 4) ? cz - 1 - 4 * k4 : 4 * k4, dk = (flip & 4) ? -1 : 1;
+  const int pi = (MIRROR && (flip & 1)) ? cx - 1 - i : i, pj = (MIRROR && (flip & 2)) ? cy - 1 - j : j;
+  const int pk0 = (MIRROR && (flip & 4)) ? cz - 1 - 4 * k4 : 4 * k4, dk = (MIRROR && (flip & 4)) ? -1 : 1;
   const int64_t x = (int64_t)starts[p * 3] + pi, y = (int64_t)starts[p * 3 + 1] + pj, z0 = (int64_t)starts[p * 3 + 2] + pk0;
   const bool row_in = x >= 0 && x < X && y >= 0 && y < Y;
   const T* __restrict__ src = img + (((int64_t)c * X + (row_in ? x : 0)) * Y + (row_in ? y : 0)) * Z;
@@ -226,11 +186,31 @@ __global__ void __launch_bounds__(SB_THREADS) seg_cut_mirror_kernel(const T* __r
   *reinterpret_cast<float4*>(out + q * 4) = o;
 }
 
+// The checks and the launch both cutters share; `who` is the entry point's name in the messages.
+template <bool MIRROR>
+int seg_cut_launch(const char* who, const void* img, int src_half, const int* starts, float* out, int n, int C, int X, int Y, int Z, int cx, int cy, int cz,
+                   int flip, pcrl_stream_t stream) {
+  PCRL_REQUIRE(img && starts && out, "%s: null pointer", who);
+  PCRL_REQUIRE(reinterpret_cast<uintptr_t>(out) % 16 == 0, "%s: out must be 16-byte aligned (16-byte stores)", who);
+  PCRL_REQUIRE(n > 0 && C > 0 && X > 0 && Y > 0 && Z > 0, "%s: bad sizes n=%d C=%d volume %d x %d x %d", who, n, C, X, Y, Z);
+  PCRL_REQUIRE(cx > 0 && cy > 0 && cz > 0 && cz % 4 == 0, "%s: bad crop %d x %d x %d (cz is a multiple of 4)", who, cx, cy, cz);
+  const int64_t total = (int64_t)n * C * cx * cy * (cz / 4), blocks = (total + SB_THREADS - 1) / SB_THREADS;
+  PCRL_REQUIRE(blocks < ((int64_t)1 << 31), "%s: too many output voxels in one call", who);
+  hipStream_t st = as_stream(stream);
+  if (src_half)
+    hipLaunchKernelGGL((seg_cut_kernel<_Float16, MIRROR>), dim3((unsigned)blocks), dim3(SB_THREADS), 0, st, static_cast<const _Float16*>(img), starts, out,
+                       total, C, X, Y, Z, cx, cy, cz, flip);
+  else
+    hipLaunchKernelGGL((seg_cut_kernel<float, MIRROR>), dim3((unsigned)blocks), dim3(SB_THREADS), 0, st, static_cast<const float*>(img), starts, out, total, C,
+                       X, Y, Z, cx, cy, cz, flip);
+  return pcrl_check_launch(who);
+}
+
 }  // namespace
 
 extern "C" size_t pcrl_seg_blend_ws_bytes(int X, int Y, int Z) {
   if (X <= 0 || Y <= 0 || Z <= 0) return 0;
-  return (size_t)sb_blocks((int64_t)X * Y * Z) * PCRL_SEG_SLOTS * sizeof(double);
+  return (size_t)capped_blocks((int64_t)X * Y * Z, SB_THREADS, SB_MAX_BLOCKS) * PCRL_SEG_SLOTS * sizeof(double);
 }
 
 extern "C" int pcrl_seg_blend(const float* z, int64_t P, const int* sx, const int* sy, const int* sz, int nx, int ny, int nz, const float* wx,
@@ -248,19 +228,11 @@ extern "C" int pcrl_seg_blend(const float* z, int64_t P, const int* sx, const in
   const bool stats = sums != nullptr;
   if (stats && (!ws || ws_bytes < pcrl_seg_blend_ws_bytes(X, Y, Z))) return pcrl_fail(PCRL_EWORKSPACE, "seg_blend: workspace too small");
   const SbGeom g{X, Y, Z, cx, cy, cz, nx, ny, nz};
-  const int nb = sb_blocks((int64_t)X * Y * Z);
+  const int nb = capped_blocks((int64_t)X * Y * Z, SB_THREADS, SB_MAX_BLOCKS);
   double* partial = static_cast<double*>(ws);
   hipStream_t st = as_stream(stream);
 #define SB_BLEND(KK) seg_blend_launch<KK>(stats, nb, st, z, sx, sy, sz, wx, wy, wz, g, labels, mask, probs, numden, counts, partial)
-  switch (K) {
-    case 1: SB_BLEND(1); break;
-    case 2: SB_BLEND(2); break;
-    case 3: SB_BLEND(3); break;
-    case 4: SB_BLEND(4); break;
-    case 5: SB_BLEND(5); break;
-    case 6: SB_BLEND(6); break;
-    default: SB_BLEND(7); break;
-  }
+  PCRL_SEG_DISPATCH_K(SB_BLEND)
 #undef SB_BLEND
   if (stats) pcrl_seg_sums_launch(partial, nb, K, wb, wd, sums, loss, st);
   return pcrl_check_launch("seg_blend");
@@ -268,37 +240,11 @@ extern "C" int pcrl_seg_blend(const float* z, int64_t P, const int* sx, const in
 
 extern "C" int pcrl_seg_cut_patches(const void* img, int src_half, const int* starts, float* out, int n, int C, int X, int Y, int Z, int cx, int cy, int cz,
                                     pcrl_stream_t stream) {
-  PCRL_REQUIRE(img && starts && out, "seg_cut_patches: null pointer");
-  PCRL_REQUIRE(reinterpret_cast<uintptr_t>(out) % 16 == 0, "seg_cut_patches: out must be 16-byte aligned (16-byte stores)");
-  PCRL_REQUIRE(n > 0 && C > 0 && X > 0 && Y > 0 && Z > 0, "seg_cut_patches: bad sizes n=%d C=%d volume %d x %d x %d", n, C, X, Y, Z);
-  PCRL_REQUIRE(cx > 0 && cy > 0 && cz > 0 && cz % 4 == 0, "seg_cut_patches: bad crop %d x %d x %d (cz is a multiple of 4)", cx, cy, cz);
-  const int64_t total = (int64_t)n * C * cx * cy * (cz / 4), blocks = (total + SB_THREADS - 1) / SB_THREADS;
-  PCRL_REQUIRE(blocks < ((int64_t)1 << 31), "seg_cut_patches: too many output voxels in one call");
-  hipStream_t st = as_stream(stream);
-  if (src_half)
-    hipLaunchKernelGGL(seg_cut_kernel<_Float16>, dim3((unsigned)blocks), dim3(SB_THREADS), 0, st, static_cast<const _Float16*>(img), starts, out, total, C, X, Y,
-                       Z, cx, cy, cz);
-  else
-    hipLaunchKernelGGL(seg_cut_kernel<float>, dim3((unsigned)blocks), dim3(SB_THREADS), 0, st, static_cast<const float*>(img), starts, out, total, C, X, Y, Z, cx,
-                       cy, cz);
-  return pcrl_check_launch("seg_cut_patches");
+  return seg_cut_launch<false>("seg_cut_patches", img, src_half, starts, out, n, C, X, Y, Z, cx, cy, cz, 0, stream);
 }
 
 extern "C" int pcrl_seg_cut_patches_mirror(const void* img, int src_half, const int* starts, float* out, int n, int C, int X, int Y, int Z, int cx, int cy,
                                            int cz, int flip, pcrl_stream_t stream) {
   PCRL_REQUIRE(flip >= 0 && flip <= 7, "seg_cut_patches_mirror: flip %d is no mirror code (bit 0 = x, bit 1 = y, bit 2 = z: 0..7)", flip);
-  PCRL_REQUIRE(img && starts && out, "seg_cut_patches_mirror: null pointer");
-  PCRL_REQUIRE(reinterpret_cast<uintptr_t>(out) % 16 == 0, "seg_cut_patches_mirror: out must be 16-byte aligned (16-byte stores)");
-  PCRL_REQUIRE(n > 0 && C > 0 && X > 0 && Y > 0 && Z > 0, "seg_cut_patches_mirror: bad sizes n=%d C=%d volume %d x %d x %d", n, C, X, Y, Z);
-  PCRL_REQUIRE(cx > 0 && cy > 0 && cz > 0 && cz % 4 == 0, "seg_cut_patches_mirror: bad crop %d x %d x %d (cz is a multiple of 4)", cx, cy, cz);
-  const int64_t total = (int64_t)n * C * cx * cy * (cz / 4), blocks = (total + SB_THREADS - 1) / SB_THREADS;
-  PCRL_REQUIRE(blocks < ((int64_t)1 << 31), "seg_cut_patches_mirror: too many output voxels in one call");
-  hipStream_t st = as_stream(stream);
-  if (src_half)
-    hipLaunchKernelGGL(seg_cut_mirror_kernel<_Float16>, dim3((unsigned)blocks), dim3(SB_THREADS), 0, st, static_cast<const _Float16*>(img), starts, out, total,
-                       C, X, Y, Z, cx, cy, cz, flip);
-  else
-    hipLaunchKernelGGL(seg_cut_mirror_kernel<float>, dim3((unsigned)blocks), dim3(SB_THREADS), 0, st, static_cast<const float*>(img), starts, out, total, C, X,
-                       Y, Z, cx, cy, cz, flip);
-  return pcrl_check_launch("seg_cut_patches_mirror");
+  return seg_cut_launch<true>("seg_cut_patches_mirror", img, src_half, starts, out, n, C, X, Y, Z, cx, cy, cz, flip, stream);
 }

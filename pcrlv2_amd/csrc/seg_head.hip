@@ -76,8 +76,6 @@ __device__ __forceinline__ float sh_logit(const Vec16<T>& x, const float (&w)[K]
   return z + bk;
 }
 
-__device__ __forceinline__ float sh_sigmoid(float z) { return 1.0f / (1.0f + expf(-z)); }
-
 template <typename T>
 __device__ __forceinline__ void sh_fetch(const T* __restrict__ a, const uint8_t* __restrict__ labels, int64_t base, int s, int S, int sub, Vec16<T>& x,
                                          unsigned& lab) {
@@ -129,7 +127,7 @@ __global__ void __launch_bounds__(SH_THREADS) seg_head_fwd_kernel(const T* __res
     const bool counted = sub < K && !(lab & 0x80u);
     const bool g = (lab >> sub) & 1u;
     if (counted) {
-      const float p = sh_sigmoid(z), y = g ? 1.0f : 0.0f;
+      const float p = seg_sigmoid(z), y = g ? 1.0f : 0.0f;
       sI += (double)(g ? p : 0.0f);
       sP += (double)p;
       sG += (double)y;
@@ -264,7 +262,7 @@ __global__ void __launch_bounds__(SH_THREADS) seg_head_bwd_kernel(const T* __res
     const float z = sh_logit<T, K>(x, w, bk, sub);
     float dz = 0.0f;
     if (sub < K && !(lab & 0x80u)) {
-      const float p = sh_sigmoid(z), y = ((lab >> sub) & 1u) ? 1.0f : 0.0f;
+      const float p = seg_sigmoid(z), y = ((lab >> sub) & 1u) ? 1.0f : 0.0f;
       dz = cA * (p - y) - p * (1.0f - p) * (y * e1 - e0);
     }
     sdb += dz;
@@ -445,17 +443,6 @@ void seg_head_launch_bwd(dim3 grid, hipStream_t st, const void* a, const float* 
                      static_cast<T*>(dx), partial, S);
 }
 
-#define SH_DISPATCH_K(CALL)                  \
-  switch (K) {                               \
-    case 1: CALL(1); break;                  \
-    case 2: CALL(2); break;                  \
-    case 3: CALL(3); break;                  \
-    case 4: CALL(4); break;                  \
-    case 5: CALL(5); break;                  \
-    case 6: CALL(6); break;                  \
-    default: CALL(7); break;                 \
-  }
-
 int seg_head_forward(const char* what, bool eval, const void* a, const float* w, const float* b, const uint8_t* labels, const int* case_index, int64_t* counts,
                      int n_cases, uint8_t* mask, double* sums, float* loss, float wb, float wd, void* ws, size_t ws_bytes, int N, int64_t S, int K, int dtype,
                      pcrl_stream_t stream) {
@@ -469,7 +456,7 @@ int seg_head_forward(const char* what, bool eval, const void* a, const float* w,
 #define SH_FWD(KK)                                                                                                                   \
   if (dtype == PCRL_BF16) seg_head_launch_fwd<bf16, KK>(eval, grid, st, a, w, b, labels, partial, case_index, counts, n_cases, mask, (int)S); \
   else seg_head_launch_fwd<float, KK>(eval, grid, st, a, w, b, labels, partial, case_index, counts, n_cases, mask, (int)S)
-  SH_DISPATCH_K(SH_FWD)
+  PCRL_SEG_DISPATCH_K(SH_FWD)
 #undef SH_FWD
   pcrl_seg_sums_launch(partial, gx * N, K, wb, wd, sums, loss, st);
   return pcrl_check_launch(what);
@@ -503,7 +490,7 @@ extern "C" int pcrl_seg_head_logits(const void* a, const float* w, const float* 
 #define SH_LOGITS(KK)                                                                                  \
   if (dtype == PCRL_BF16) seg_head_launch_logits<bf16, KK>(grid, st, a, w, b, z, (int)S);             \
   else seg_head_launch_logits<float, KK>(grid, st, a, w, b, z, (int)S)
-  SH_DISPATCH_K(SH_LOGITS)
+  PCRL_SEG_DISPATCH_K(SH_LOGITS)
 #undef SH_LOGITS
   return pcrl_check_launch("seg_head_logits");
 }
@@ -521,7 +508,7 @@ extern "C" int pcrl_seg_head_logits_acc(const void* a, const float* w, const flo
 #define SH_LOGITS_ACC(KK)                                                                                                  \
   if (dtype == PCRL_BF16) seg_head_launch_logits_acc<bf16, KK>(first != 0, grid, st, a, w, b, z, (int)S, m, scale);       \
   else seg_head_launch_logits_acc<float, KK>(first != 0, grid, st, a, w, b, z, (int)S, m, scale)
-  SH_DISPATCH_K(SH_LOGITS_ACC)
+  PCRL_SEG_DISPATCH_K(SH_LOGITS_ACC)
 #undef SH_LOGITS_ACC
   return pcrl_check_launch("seg_head_logits_acc");
 }
@@ -557,7 +544,7 @@ extern "C" int pcrl_seg_head_bwd(const void* a, const float* w, const float* b, 
 #define SH_BWD(KK)                                                                                                        \
   if (dtype == PCRL_BF16) seg_head_launch_bwd<bf16, KK>(grid, st, a, w, b, labels, sums, dloss, wb, wd, dx, partial, (int)S); \
   else seg_head_launch_bwd<float, KK>(grid, st, a, w, b, labels, sums, dloss, wb, wd, dx, partial, (int)S)
-  SH_DISPATCH_K(SH_BWD)
+  PCRL_SEG_DISPATCH_K(SH_BWD)
 #undef SH_BWD
   hipLaunchKernelGGL(seg_head_wsum_kernel, dim3((sh_wstride(K) + 63) / 64), dim3(SH_THREADS), 0, st, partial, gx * N, K, dw, db);
   return pcrl_check_launch("seg_head_bwd");

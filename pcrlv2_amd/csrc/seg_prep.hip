@@ -11,7 +11,7 @@
 //                          sum((x - mean)^2) / n.  Per thread a grid-stride sum, a 64-lane shuffle tree, four wave partials added in wave order,
 //                          one partial per (block, channel); a one-block second launch adds them in block order (seg_head.hip's scheme).  The grid
 //                          is a function of the voxel count alone, so the result is a function of the sizes and the data, never of timing.
-//   pcrl_segprep_select    exact order statistics of one channel's masked values for four ranks at once: surface_dist.hip's radix select on the
+//   pcrl_segprep_select    exact order statistics of one channel's masked values for four ranks at once: radix_select.h's selection on the
 //                          32-bit order-preserving key of the float32 value (all bits of a negative flipped, the sign bit of the rest; -0.0 takes
 //                          +0.0's key and comes back as +0.0): four byte passes, most significant first, each a 256-bin LDS histogram per rank
 //                          (LDS integer atomics, then one 64-bit integer atomic per non-empty (block, rank, bin)) and a four-thread `pick` launch.
@@ -47,7 +47,7 @@
 //           float64 divisions.  (An even pitch would put every second row on the same bank; a power of two all of them.)  The byte tiles are
 //           read as `ds_read_u8`, four rows' bytes per dword: lanes with equal dword broadcast, the others are at most 2-way by the same argument.
 // Every output element is written once, by one thread; no floating-point atomics anywhere in this file: two runs give identical bytes.
-#include "common.h"
+#include "radix_select.h"
 
 namespace {
 
@@ -55,36 +55,7 @@ constexpr int SP_THREADS = 256, SP_MAX_BLOCKS = 1024, SP_MAX_C = 16, SP_MAX_K = 
 constexpr int SP_TILE = 32, SP_LDS_BUDGET = 40 * 1024;
 constexpr unsigned long long SP_BOX_EMPTY = 0x7fffffffull;
 
-inline int sp_blocks(int64_t items) {
-  const int64_t want = (items + SP_THREADS - 1) / SP_THREADS;
-  return (int)(want < 1 ? 1 : want < SP_MAX_BLOCKS ? want : SP_MAX_BLOCKS);
-}
-inline bool sp_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-  return a && b && pa < pb + nb && pb < pa + na;
-}
 __device__ __forceinline__ int sp_clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-__device__ __forceinline__ unsigned sp_wave_sum(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int sp_wave_min(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int w = __shfl_xor(v, o, 64);
-    v = w < v ? w : v;
-  }
-  return v;
-}
-__device__ __forceinline__ int sp_wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int w = __shfl_xor(v, o, 64);
-    v = w > v ? w : v;
-  }
-  return v;
-}
 __device__ __forceinline__ bool sp_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 __device__ __forceinline__ bool sp_finite(int16_t) { return true; }
 
@@ -122,14 +93,14 @@ __global__ void __launch_bounds__(SP_THREADS) sp_scan_kernel(const T* __restrict
   }
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    const int l = sp_wave_min(lo[a]), h = sp_wave_max(hi[a]);
+    const int l = wave_min(lo[a]), h = wave_max(hi[a]);
     if (lane == 0) {
       red[wid][2 * a] = l;
       red[wid][2 * a + 1] = h;
     }
   }
-  cnt = sp_wave_sum(cnt);
-  bad = sp_wave_sum(bad);
+  cnt = wave_sum(cnt);
+  bad = wave_sum(bad);
   if (lane == 0) {
     red[wid][6] = (int)cnt;
     red[wid][7] = (int)bad;
@@ -212,12 +183,7 @@ __global__ void sp_sum_final_kernel(const double* __restrict__ partial, int nb, 
 }
 
 // ---- select -------------------------------------------------------------------------------------------------------------------------
-struct SpSel {
-  unsigned long long rank[4];
-  unsigned prefix[4];
-  unsigned pad[4];
-  unsigned long long hist[4][256];
-};
+using SpSel = RadixSelect<uint32_t, 4>;
 
 __device__ __forceinline__ unsigned sp_key(float v) {
   unsigned b = __float_as_uint(v);
@@ -238,47 +204,25 @@ __global__ void sp_sel_init_kernel(SpSel* __restrict__ st, long long r0, long lo
 template <typename T>
 __global__ void __launch_bounds__(SP_THREADS) sp_hist_kernel(const T* __restrict__ src, int C, int ch, int64_t V, int use_mask, int pass, SpSel* __restrict__ st) {
   __shared__ unsigned h[4 * 256];
-  const int t = threadIdx.x;
-  for (int i = t; i < 4 * 256; i += SP_THREADS) h[i] = 0u;
-  const unsigned p0 = st->prefix[0], p1 = st->prefix[1], p2 = st->prefix[2], p3 = st->prefix[3];
-  __syncthreads();
-  const int shift = 24 - 8 * pass;
-  for (int64_t v = (int64_t)blockIdx.x * SP_THREADS + t; v < V; v += (int64_t)gridDim.x * SP_THREADS) {
+  RadixPass<uint32_t, 4, SP_THREADS> rp;
+  rp.begin(st, pass, h);
+  for (int64_t v = (int64_t)blockIdx.x * SP_THREADS + threadIdx.x; v < V; v += (int64_t)gridDim.x * SP_THREADS) {
     if (use_mask) {
       bool nz = false;
       for (int c = 0; c < C; ++c) nz = nz || ((float)src[(int64_t)c * V + v] != 0.0f);
       if (!nz) continue;
     }
-    const unsigned k = sp_key((float)src[(int64_t)ch * V + v]);
-    const unsigned byte = (k >> shift) & 255u;
-    const unsigned head = pass ? k >> (shift + 8) : 0u;
-    if (head == p0) atomicAdd(&h[byte], 1u);
-    if (head == p1) atomicAdd(&h[256 + byte], 1u);
-    if (head == p2) atomicAdd(&h[512 + byte], 1u);
-    if (head == p3) atomicAdd(&h[768 + byte], 1u);
+    rp.add(sp_key((float)src[(int64_t)ch * V + v]));
   }
-  __syncthreads();
-  unsigned long long* gh = &st->hist[0][0];
-  for (int i = t; i < 4 * 256; i += SP_THREADS)
-    if (h[i]) atomicAdd(&gh[i], (unsigned long long)h[i]);
+  rp.flush(st);
 }
 
-// one block of 64 threads; thread r < 4 walks the bins of rank r, extends its prefix by the byte that holds the rank, and clears its histogram
-__global__ void sp_pick_kernel(SpSel* __restrict__ st, int pass, float* __restrict__ out) {
+// one block of 64 threads; thread r < 4 picks rank r, and after the last pass turns its key back into the value
+__global__ void sp_sel_pick_kernel(SpSel* __restrict__ st, int pass, float* __restrict__ out) {
   const int r = threadIdx.x;
   if (r >= 4) return;
-  unsigned long long rank = st->rank[r], cum = 0;
-  int b = 0;
-  for (; b < 255; ++b) {
-    const unsigned long long c = st->hist[r][b];
-    if (rank < cum + c) break;
-    cum += c;
-  }
-  for (int i = 0; i < 256; ++i) st->hist[r][i] = 0;
-  const unsigned pre = (st->prefix[r] << 8) | (unsigned)b;
-  st->rank[r] = rank - cum;
-  st->prefix[r] = pre;
-  if (pass == 3) out[r] = sp_unkey(pre);
+  const uint32_t pre = radix_pick(st, r);
+  if (pass == SpSel::PASSES - 1) out[r] = sp_unkey(pre);
 }
 
 // ---- resample -----------------------------------------------------------------------------------------------------------------------
@@ -457,19 +401,19 @@ extern "C" int pcrl_segprep_scan(const void* src, int src_kind, int C, int X, in
   PCRL_REQUIRE(sp_grid_ok(X, Y, Z), "segprep_scan: volume %d x %d x %d (every extent >= 1, fewer than 2^31 voxels)", X, Y, Z);
   PCRL_REQUIRE(src && rec, "segprep_scan: null pointer");
   const int64_t V = (int64_t)X * Y * Z;
-  PCRL_REQUIRE(!sp_overlap(src, (size_t)V * C * (src_kind ? 4 : 2), rec, 64), "segprep_scan: rec overlaps src");
+  PCRL_REQUIRE(!ranges_overlap(src, (size_t)V * C * (src_kind ? 4 : 2), rec, 64), "segprep_scan: rec overlaps src");
   PCRL_REQUIRE(reinterpret_cast<uintptr_t>(rec) % 8 == 0, "segprep_scan: rec must be 8-byte aligned");
   hipStream_t s = as_stream(stream);
   unsigned long long* r = reinterpret_cast<unsigned long long*>(rec);
   hipLaunchKernelGGL(sp_scan_init_kernel, dim3(1), dim3(64), 0, s, r);
-  if (src_kind) hipLaunchKernelGGL(sp_scan_kernel<float>, dim3(sp_blocks(V)), dim3(SP_THREADS), 0, s, static_cast<const float*>(src), C, X, Y, V, r);
-  else hipLaunchKernelGGL(sp_scan_kernel<int16_t>, dim3(sp_blocks(V)), dim3(SP_THREADS), 0, s, static_cast<const int16_t*>(src), C, X, Y, V, r);
+  if (src_kind) hipLaunchKernelGGL(sp_scan_kernel<float>, dim3(capped_blocks(V, SP_THREADS, SP_MAX_BLOCKS)), dim3(SP_THREADS), 0, s, static_cast<const float*>(src), C, X, Y, V, r);
+  else hipLaunchKernelGGL(sp_scan_kernel<int16_t>, dim3(capped_blocks(V, SP_THREADS, SP_MAX_BLOCKS)), dim3(SP_THREADS), 0, s, static_cast<const int16_t*>(src), C, X, Y, V, r);
   return pcrl_check_launch("segprep_scan");
 }
 
 extern "C" size_t pcrl_segprep_stats_ws_bytes(int C, int64_t V) {
   if (C < 1 || C > SP_MAX_C || V < 1) return 0;
-  return (size_t)sp_blocks(V) * C * sizeof(double);
+  return (size_t)capped_blocks(V, SP_THREADS, SP_MAX_BLOCKS) * C * sizeof(double);
 }
 
 extern "C" int pcrl_segprep_stats(const void* src, int src_kind, int C, int X, int Y, int Z, int use_mask, const int64_t* rec, const double* clip,
@@ -480,12 +424,12 @@ extern "C" int pcrl_segprep_stats(const void* src, int src_kind, int C, int X, i
   PCRL_REQUIRE(src && stats && (rec || !use_mask), "segprep_stats: null pointer");
   const int64_t V = (int64_t)X * Y * Z;
   const size_t nsrc = (size_t)V * C * (src_kind ? 4 : 2);
-  PCRL_REQUIRE(!sp_overlap(src, nsrc, stats, (size_t)C * 16) && !sp_overlap(src, nsrc, ws, ws_bytes) && !sp_overlap(stats, (size_t)C * 16, ws, ws_bytes),
+  PCRL_REQUIRE(!ranges_overlap(src, nsrc, stats, (size_t)C * 16) && !ranges_overlap(src, nsrc, ws, ws_bytes) && !ranges_overlap(stats, (size_t)C * 16, ws, ws_bytes),
                "segprep_stats: overlapping buffers");
   if (!ws || ws_bytes < pcrl_segprep_stats_ws_bytes(C, V)) return pcrl_fail(PCRL_EWORKSPACE, "segprep_stats: workspace too small");
   PCRL_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 8 == 0 && reinterpret_cast<uintptr_t>(stats) % 8 == 0, "segprep_stats: stats and ws must be 8-byte aligned");
   hipStream_t s = as_stream(stream);
-  const int nb = sp_blocks(V);
+  const int nb = capped_blocks(V, SP_THREADS, SP_MAX_BLOCKS);
   double* partial = static_cast<double*>(ws);
   const unsigned long long* r = reinterpret_cast<const unsigned long long*>(rec);
   if (src_kind) {
@@ -517,15 +461,15 @@ extern "C" int pcrl_segprep_select(const void* src, int src_kind, int C, int ch,
   if (!ws || ws_bytes < sizeof(SpSel)) return pcrl_fail(PCRL_EWORKSPACE, "segprep_select: workspace too small");
   PCRL_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 8 == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0, "segprep_select: ws must be 8-byte, out 4-byte aligned");
   const size_t nsrc = (size_t)V * C * (src_kind ? 4 : 2);
-  PCRL_REQUIRE(!sp_overlap(src, nsrc, out, 16) && !sp_overlap(src, nsrc, ws, ws_bytes) && !sp_overlap(out, 16, ws, ws_bytes), "segprep_select: overlapping buffers");
+  PCRL_REQUIRE(!ranges_overlap(src, nsrc, out, 16) && !ranges_overlap(src, nsrc, ws, ws_bytes) && !ranges_overlap(out, 16, ws, ws_bytes), "segprep_select: overlapping buffers");
   hipStream_t s = as_stream(stream);
   SpSel* st = static_cast<SpSel*>(ws);
-  const int nb = sp_blocks(V);
+  const int nb = capped_blocks(V, SP_THREADS, SP_MAX_BLOCKS);
   hipLaunchKernelGGL(sp_sel_init_kernel, dim3(1), dim3(256), 0, s, st, (long long)r0, (long long)r1, (long long)r2, (long long)r3);
-  for (int pass = 0; pass < 4; ++pass) {
+  for (int pass = 0; pass < SpSel::PASSES; ++pass) {
     if (src_kind) hipLaunchKernelGGL(sp_hist_kernel<float>, dim3(nb), dim3(SP_THREADS), 0, s, static_cast<const float*>(src), C, ch, V, use_mask, pass, st);
     else hipLaunchKernelGGL(sp_hist_kernel<int16_t>, dim3(nb), dim3(SP_THREADS), 0, s, static_cast<const int16_t*>(src), C, ch, V, use_mask, pass, st);
-    hipLaunchKernelGGL(sp_pick_kernel, dim3(1), dim3(64), 0, s, st, pass, out);
+    hipLaunchKernelGGL(sp_sel_pick_kernel, dim3(1), dim3(64), 0, s, st, pass, out);
   }
   return pcrl_check_launch("segprep_select");
 }
@@ -564,14 +508,14 @@ extern "C" int pcrl_segprep_resample(const void* src, int src_kind, const uint8_
   PCRL_REQUIRE(src && tab_i && tab_w && img && lab && (region || !src_lab), "segprep_resample: null pointer");
   const int64_t V = (int64_t)X * Y * Z, OV = (int64_t)OX * OY * OZ;
   const size_t nsrc = (size_t)V * C * (src_kind ? 4 : 2), nimg = (size_t)OV * C * (out_half ? 2 : 4);
-  PCRL_REQUIRE(!sp_overlap(img, nimg, src, nsrc) && !sp_overlap(img, nimg, src_lab, (size_t)V) && !sp_overlap(lab, (size_t)OV, src, nsrc) &&
-                   !sp_overlap(lab, (size_t)OV, src_lab, (size_t)V) && !sp_overlap(img, nimg, lab, (size_t)OV),
+  PCRL_REQUIRE(!ranges_overlap(img, nimg, src, nsrc) && !ranges_overlap(img, nimg, src_lab, (size_t)V) && !ranges_overlap(lab, (size_t)OV, src, nsrc) &&
+                   !ranges_overlap(lab, (size_t)OV, src_lab, (size_t)V) && !ranges_overlap(img, nimg, lab, (size_t)OV),
                "segprep_resample: img or lab overlaps a source or the other output");
   const size_t nti = (size_t)3 * ((size_t)OX + OY + OZ) * 4, ntw = (size_t)2 * ((size_t)OX + OY + OZ) * 8;
-  PCRL_REQUIRE(!sp_overlap(img, nimg, tab_i, nti) && !sp_overlap(img, nimg, tab_w, ntw) && !sp_overlap(lab, (size_t)OV, tab_i, nti) &&
-                   !sp_overlap(lab, (size_t)OV, tab_w, ntw) && !sp_overlap(img, nimg, stats, (size_t)C * 16) && !sp_overlap(img, nimg, clip, (size_t)C * 16) &&
-                   !sp_overlap(lab, (size_t)OV, stats, (size_t)C * 16) && !sp_overlap(lab, (size_t)OV, clip, (size_t)C * 16) &&
-                   !sp_overlap(img, nimg, region, 256) && !sp_overlap(lab, (size_t)OV, region, 256),
+  PCRL_REQUIRE(!ranges_overlap(img, nimg, tab_i, nti) && !ranges_overlap(img, nimg, tab_w, ntw) && !ranges_overlap(lab, (size_t)OV, tab_i, nti) &&
+                   !ranges_overlap(lab, (size_t)OV, tab_w, ntw) && !ranges_overlap(img, nimg, stats, (size_t)C * 16) && !ranges_overlap(img, nimg, clip, (size_t)C * 16) &&
+                   !ranges_overlap(lab, (size_t)OV, stats, (size_t)C * 16) && !ranges_overlap(lab, (size_t)OV, clip, (size_t)C * 16) &&
+                   !ranges_overlap(img, nimg, region, 256) && !ranges_overlap(lab, (size_t)OV, region, 256),
                "segprep_resample: img or lab overlaps a table");
   PCRL_REQUIRE(reinterpret_cast<uintptr_t>(src) % (src_kind ? 4 : 2) == 0 && reinterpret_cast<uintptr_t>(img) % (out_half ? 2 : 4) == 0 &&
                    reinterpret_cast<uintptr_t>(tab_i) % 4 == 0 && reinterpret_cast<uintptr_t>(tab_w) % 8 == 0 &&
@@ -602,11 +546,11 @@ extern "C" int pcrl_segprep_restore(const uint8_t* pred, int PX, int PY, int PZ,
                "segprep_restore: box [%d, +%d) x [%d, +%d) x [%d, +%d) is empty or outside the volume %d x %d x %d", bx, NX, by, NY, bz, NZ, X, Y, Z);
   PCRL_REQUIRE(pred && tab && out && (paint || !painted), "segprep_restore: null pointer");
   const size_t V = (size_t)X * Y * Z, PV = (size_t)PX * PY * PZ, nt = ((size_t)NX + NY + NZ) * 4;
-  PCRL_REQUIRE(!sp_overlap(out, V, pred, PV) && !sp_overlap(out, V, tab, nt) && !sp_overlap(out, V, paint, 256) && !sp_overlap(painted, V, pred, PV) &&
-                   !sp_overlap(painted, V, tab, nt) && !sp_overlap(painted, V, paint, 256) && !sp_overlap(out, V, painted, V),
+  PCRL_REQUIRE(!ranges_overlap(out, V, pred, PV) && !ranges_overlap(out, V, tab, nt) && !ranges_overlap(out, V, paint, 256) && !ranges_overlap(painted, V, pred, PV) &&
+                   !ranges_overlap(painted, V, tab, nt) && !ranges_overlap(painted, V, paint, 256) && !ranges_overlap(out, V, painted, V),
                "segprep_restore: overlapping buffers");
   PCRL_REQUIRE(reinterpret_cast<uintptr_t>(tab) % 4 == 0, "segprep_restore: tab must be 4-byte aligned");
-  hipLaunchKernelGGL(sp_restore_kernel, dim3(sp_blocks((int64_t)V)), dim3(SP_THREADS), 0, as_stream(stream), pred, PX, PY, PZ, tab, bx, by, bz, NX, NY, NZ, paint,
+  hipLaunchKernelGGL(sp_restore_kernel, dim3(capped_blocks((int64_t)V, SP_THREADS, SP_MAX_BLOCKS)), dim3(SP_THREADS), 0, as_stream(stream), pred, PX, PY, PZ, tab, bx, by, bz, NX, NY, NZ, paint,
                      out, painted, X, Y, Z);
   return pcrl_check_launch("segprep_restore");
 }

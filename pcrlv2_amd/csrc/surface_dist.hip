@@ -24,30 +24,19 @@
 //           on one of ds_read_b32's 32 banks: at worst 2-way, once per element.  The
 //           stores that fill the tile are 64 consecutive float64 per wave as well.
 // stats     count: one pass over both (mask, d2) pairs -- n_a, n_b (integer atomics) and the two sums of sqrt(d2): per-thread float64, wave shuffle,
-//           LDS red[wave][2], per-block partials that the one-thread `start` launch adds in block order.  select: radix select on the 64-bit
+//           LDS red[wave][2], per-block partials that the one-thread `start` launch adds in block order.  select: radix select (radix_select.h) on the 64-bit
 //           pattern of the non-negative doubles (their order is the integers' order), most significant byte first: eight passes, each a 256-bin
 //           histogram PER RANK (lo, hi, n - 1) of the values that share the rank's prefix so far -- LDS integer atomics, then one 64-bit integer
 //           atomic per non-empty (block, rank, bin) -- and a tiny `pick` launch that walks the bins, extends the prefixes and clears the
 //           histogram.  No host read-back in between, no floating-point atomics: the result does not depend on any order.  The LDS traffic of a
 //           histogram is atomics on data-dependent bins; equal values serialise on one bin, which is what counting them takes.
-#include "common.h"
+#include "radix_select.h"
 
 namespace {
 
 constexpr int SD_THREADS = 256, SD_MAX_K = 7, SD_MAX_BLOCKS = 1024;
 constexpr int SE_ZPT = 4;
 constexpr int EDT_THREADS = 512, EDT_LDS = 8128, EDT_INNER_TILE = 4096, EDT_INNER_LINES = 512, EDT_MAX_RUN = 64, EDT_MAX_AXIS = 1024;
-
-__device__ __forceinline__ unsigned sd_wave_sum(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
-  return v;
-}
-
-inline int sd_blocks(int64_t items) {
-  const int64_t want = (items + SD_THREADS - 1) / SD_THREADS;
-  return (int)(want < SD_MAX_BLOCKS ? want : SD_MAX_BLOCKS);
-}
 
 // ---- surface extraction -------------------------------------------------------------------------------------------------------------
 // prediction in bits 0..6, ground truth in bits 8..14 of one word; a voxel that is not counted belongs to neither mask
@@ -57,7 +46,7 @@ __device__ __forceinline__ unsigned se_eff(const uint8_t* __restrict__ pred, con
   return (p & keep) | ((g & keep) << 8);
 }
 
-// grid = sd_blocks(X * Y * ceil(Z / 4)); block = 256.  VEC: Z % 4 == 0 and both outputs 4-byte aligned -- one 32-bit store per thread and mask.
+// grid = capped_blocks(X * Y * ceil(Z / 4), 256, SD_MAX_BLOCKS); block = 256.  VEC: Z % 4 == 0 and both outputs 4-byte aligned -- one 32-bit store per thread and mask.
 template <bool VEC>
 __global__ void __launch_bounds__(SD_THREADS) surf_extract_kernel(const uint8_t* __restrict__ pred, const uint8_t* __restrict__ gt, uint8_t* __restrict__ sp,
                                                                  uint8_t* __restrict__ sg, unsigned long long* __restrict__ counts, int X, int Y, int Z, int K) {
@@ -122,7 +111,7 @@ __global__ void __launch_bounds__(SD_THREADS) surf_extract_kernel(const uint8_t*
   }
 #pragma unroll
   for (int k = 0; k < SD_MAX_K; ++k) {
-    const unsigned p = sd_wave_sum(cTP[k]), q = sd_wave_sum(cPr[k]), g = sd_wave_sum(cGt[k]);
+    const unsigned p = wave_sum(cTP[k]), q = wave_sum(cPr[k]), g = wave_sum(cGt[k]);
     if (lane == 0) {
       redc[wid][k * 3 + 0] = p;
       redc[wid][k * 3 + 1] = q;
@@ -203,24 +192,21 @@ __global__ void __launch_bounds__(EDT_THREADS) edt_line_kernel(const uint8_t* __
     d2[INNER ? base + e : base + (int64_t)i * g.B + (e % nr)] = best;
   }
   if (steps) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+    mine = wave_sum(mine);
     if ((t & 63) == 0 && mine) atomicAdd(steps, mine);
   }
 }
 
 // ---- distance statistics of one class -------------------------------------------------------------------------------------------------
+using SdSel = RadixSelect<uint64_t, 3>;      // the ranks lo, hi, n - 1
 struct SdState {
   unsigned long long cnt[2];     // n_a, n_b
   unsigned long long active;     // both surfaces non-empty: the selection runs
-  unsigned long long rank[3];    // what is left of the ranks lo, hi, n - 1 inside the current prefix
-  unsigned long long prefix[3];  // the leading bytes found so far
-  unsigned long long pad[5];
-  unsigned long long hist[3][256];
+  SdSel sel;
 };
 constexpr size_t SD_STATE_BYTES = sizeof(SdState);
 
-// grid = sd_blocks(V); block = 256.  partial [nb][2] float64.
+// grid = capped_blocks(V, 256, SD_MAX_BLOCKS); block = 256.  partial [nb][2] float64.
 __global__ void __launch_bounds__(SD_THREADS) sd_count_kernel(const double* __restrict__ d2a, const uint8_t* __restrict__ ma, const double* __restrict__ d2b,
                                                              const uint8_t* __restrict__ mb, unsigned bit, int64_t V, SdState* __restrict__ st,
                                                              double* __restrict__ partial) {
@@ -241,8 +227,8 @@ __global__ void __launch_bounds__(SD_THREADS) sd_count_kernel(const double* __re
   }
   sa = wave_sum(sa);
   sb = wave_sum(sb);
-  na = sd_wave_sum(na);
-  nb = sd_wave_sum(nb);
+  na = wave_sum(na);
+  nb = wave_sum(nb);
   if (lane == 0) {
     red[wid][0] = sa;
     red[wid][1] = sb;
@@ -271,10 +257,10 @@ __global__ void sd_start_kernel(SdState* __restrict__ st, const double* __restri
   long long lo = (long long)floor(q * (double)(n - 1));
   lo = lo < 0 ? 0 : (lo > n - 1 ? n - 1 : lo);
   const long long hi = lo + 1 < n - 1 ? lo + 1 : n - 1;
-  st->rank[0] = (unsigned long long)lo;
-  st->rank[1] = (unsigned long long)hi;
-  st->rank[2] = (unsigned long long)(n - 1);
-  st->prefix[0] = st->prefix[1] = st->prefix[2] = 0;
+  st->sel.rank[0] = (unsigned long long)lo;
+  st->sel.rank[1] = (unsigned long long)hi;
+  st->sel.rank[2] = (unsigned long long)(n - 1);
+  st->sel.prefix[0] = st->sel.prefix[1] = st->sel.prefix[2] = 0;
   st->active = 1;
   rec[2] = lo;
   double sa = 0.0, sb = 0.0;
@@ -287,51 +273,30 @@ __global__ void sd_start_kernel(SdState* __restrict__ st, const double* __restri
   recd[7] = sb;
 }
 
-// grid = sd_blocks(V); block = 256.  pass 0 looks at the most significant byte.
+// grid = capped_blocks(V, 256, SD_MAX_BLOCKS); block = 256.  A voxel yields a key for each surface it lies on: the bit pattern of its distance.
 __global__ void __launch_bounds__(SD_THREADS) sd_hist_kernel(const double* __restrict__ d2a, const uint8_t* __restrict__ ma, const double* __restrict__ d2b,
                                                             const uint8_t* __restrict__ mb, unsigned bit, int64_t V, int pass, SdState* __restrict__ st) {
   __shared__ unsigned h[3 * 256];
   if (!st->active) return;      // uniform over the grid
-  const int t = threadIdx.x;
-  for (int i = t; i < 3 * 256; i += SD_THREADS) h[i] = 0u;
-  const unsigned long long p0 = st->prefix[0], p1 = st->prefix[1], p2 = st->prefix[2];
-  __syncthreads();
-  const int shift = 56 - 8 * pass;
-  for (int64_t v = (int64_t)blockIdx.x * SD_THREADS + t; v < V; v += (int64_t)gridDim.x * SD_THREADS) {
+  RadixPass<uint64_t, 3, SD_THREADS> rp;
+  rp.begin(&st->sel, pass, h);
+  for (int64_t v = (int64_t)blockIdx.x * SD_THREADS + threadIdx.x; v < V; v += (int64_t)gridDim.x * SD_THREADS) {
 #pragma unroll
     for (int side = 0; side < 2; ++side) {
       if (!((side ? mb[v] : ma[v]) & bit)) continue;
-      const unsigned long long u = (unsigned long long)__double_as_longlong(side ? d2b[v] : d2a[v]);
-      const unsigned byte = (unsigned)(u >> shift) & 255u;
-      const unsigned long long head = pass ? u >> (shift + 8) : 0ull;
-      if (head == p0) atomicAdd(&h[byte], 1u);
-      if (head == p1) atomicAdd(&h[256 + byte], 1u);
-      if (head == p2) atomicAdd(&h[512 + byte], 1u);
+      rp.add((uint64_t)__double_as_longlong(side ? d2b[v] : d2a[v]));
     }
   }
-  __syncthreads();
-  unsigned long long* gh = &st->hist[0][0];
-  for (int i = t; i < 3 * 256; i += SD_THREADS)
-    if (h[i]) atomicAdd(&gh[i], (unsigned long long)h[i]);
+  rp.flush(&st->sel);
 }
 
-// one block of 64 threads; thread r < 3 walks the bins of rank r, extends its prefix by the byte that holds the rank, and clears its histogram
-__global__ void sd_pick_kernel(SdState* __restrict__ st, int pass, long long* __restrict__ rec) {
+// one block of 64 threads; thread r < 3 picks rank r, and after the last pass leaves its key in the record
+__global__ void sd_sel_pick_kernel(SdState* __restrict__ st, int pass, long long* __restrict__ rec) {
   if (!st->active) return;
   const int r = threadIdx.x;
   if (r >= 3) return;
-  unsigned long long rank = st->rank[r], cum = 0;
-  int b = 0;
-  for (; b < 255; ++b) {
-    const unsigned long long c = st->hist[r][b];
-    if (rank < cum + c) break;
-    cum += c;
-  }
-  for (int i = 0; i < 256; ++i) st->hist[r][i] = 0;
-  const unsigned long long pre = (st->prefix[r] << 8) | (unsigned long long)b;
-  st->rank[r] = rank - cum;
-  st->prefix[r] = pre;
-  if (pass == 7) rec[3 + r] = (long long)pre;
+  const uint64_t pre = radix_pick(&st->sel, r);
+  if (pass == SdSel::PASSES - 1) rec[3 + r] = (long long)pre;
 }
 
 }  // namespace
@@ -341,13 +306,13 @@ extern "C" int pcrl_surf_extract(const uint8_t* pred, const uint8_t* gt, uint8_t
   PCRL_REQUIRE(K >= 1 && K <= SD_MAX_K, "surf_extract: 1 <= K <= %d classes (bit 7 of a label byte means 'not counted'), got %d", SD_MAX_K, K);
   PCRL_REQUIRE(X > 0 && Y > 0 && Z > 0, "surf_extract: empty volume %d x %d x %d", X, Y, Z);
   PCRL_REQUIRE(pred && gt && surf_pred && surf_gt && counts, "surf_extract: null pointer");
-  const int64_t items = (int64_t)X * Y * ((Z + SE_ZPT - 1) / SE_ZPT);
+  const int nb = capped_blocks((int64_t)X * Y * ((Z + SE_ZPT - 1) / SE_ZPT), SD_THREADS, SD_MAX_BLOCKS);
   const bool vec = Z % SE_ZPT == 0 && reinterpret_cast<uintptr_t>(surf_pred) % 4 == 0 && reinterpret_cast<uintptr_t>(surf_gt) % 4 == 0;
   unsigned long long* c = reinterpret_cast<unsigned long long*>(counts);
   if (vec)
-    hipLaunchKernelGGL(surf_extract_kernel<true>, dim3(sd_blocks(items)), dim3(SD_THREADS), 0, as_stream(stream), pred, gt, surf_pred, surf_gt, c, X, Y, Z, K);
+    hipLaunchKernelGGL(surf_extract_kernel<true>, dim3(nb), dim3(SD_THREADS), 0, as_stream(stream), pred, gt, surf_pred, surf_gt, c, X, Y, Z, K);
   else
-    hipLaunchKernelGGL(surf_extract_kernel<false>, dim3(sd_blocks(items)), dim3(SD_THREADS), 0, as_stream(stream), pred, gt, surf_pred, surf_gt, c, X, Y, Z, K);
+    hipLaunchKernelGGL(surf_extract_kernel<false>, dim3(nb), dim3(SD_THREADS), 0, as_stream(stream), pred, gt, surf_pred, surf_gt, c, X, Y, Z, K);
   return pcrl_check_launch("surf_extract");
 }
 
@@ -395,7 +360,7 @@ extern "C" int pcrl_edt_sq(const uint8_t* surf, int bit, double* d2, double sx, 
 
 extern "C" size_t pcrl_surf_dist_stats_ws_bytes(int64_t V) {
   if (V <= 0) return 0;
-  return SD_STATE_BYTES + (size_t)sd_blocks(V) * 2 * sizeof(double);
+  return SD_STATE_BYTES + (size_t)capped_blocks(V, SD_THREADS, SD_MAX_BLOCKS) * 2 * sizeof(double);
 }
 
 extern "C" int pcrl_surf_dist_stats(const double* d2_to_gt, const uint8_t* surf_pred, const double* d2_to_pred, const uint8_t* surf_gt, int bit, double q,
@@ -410,14 +375,14 @@ extern "C" int pcrl_surf_dist_stats(const double* d2_to_gt, const uint8_t* surf_
   SdState* state = static_cast<SdState*>(ws);
   double* partial = reinterpret_cast<double*>(static_cast<char*>(ws) + SD_STATE_BYTES);
   long long* rec = reinterpret_cast<long long*>(record);
-  const int nb = sd_blocks(V);
+  const int nb = capped_blocks(V, SD_THREADS, SD_MAX_BLOCKS);
   const unsigned b = 1u << bit;
   if (hipMemsetAsync(state, 0, SD_STATE_BYTES, st) != hipSuccess) return pcrl_fail(PCRL_EINVAL, "surf_dist_stats: memset failed");
   hipLaunchKernelGGL(sd_count_kernel, dim3(nb), dim3(SD_THREADS), 0, st, d2_to_gt, surf_pred, d2_to_pred, surf_gt, b, V, state, partial);
   hipLaunchKernelGGL(sd_start_kernel, dim3(1), dim3(64), 0, st, state, partial, nb, q, rec);
-  for (int pass = 0; pass < 8; ++pass) {
+  for (int pass = 0; pass < SdSel::PASSES; ++pass) {
     hipLaunchKernelGGL(sd_hist_kernel, dim3(nb), dim3(SD_THREADS), 0, st, d2_to_gt, surf_pred, d2_to_pred, surf_gt, b, V, pass, state);
-    hipLaunchKernelGGL(sd_pick_kernel, dim3(1), dim3(64), 0, st, state, pass, rec);
+    hipLaunchKernelGGL(sd_sel_pick_kernel, dim3(1), dim3(64), 0, st, state, pass, rec);
   }
   return pcrl_check_launch("surf_dist_stats");
 }

@@ -34,6 +34,8 @@ import os
 import numpy as np
 import torch
 
+from ._lib import call_on_stream
+
 TRAIN_FOLDS, VALID_FOLDS = (0, 1, 2, 3, 4, 5, 6), (7, 8, 9)     # data.py:67-68
 
 
@@ -167,19 +169,14 @@ def draw_swap(gen, B, dhw, device, patch=(8, 4, 4), iterations=100):
     return o.to(torch.int32).contiguous()
 
 
-def _call(name, *args):
-    from ._lib import lib, stream_handle
-    lib().call(name, *args, stream_handle())
-
-
 def apply_spatial(x, flip, inv):
     """flip + affine resampling of [B,D,H,W] float32 volumes on the device (pcrl_aug_volume_min, pcrl_aug_affine)."""
     B, D, H, W = x.shape
     x = x.contiguous()
     vmin = torch.empty(B, dtype=torch.float32, device=x.device)
-    _call("pcrl_aug_volume_min", x, vmin, B, D * H * W)
+    call_on_stream("pcrl_aug_volume_min", x, vmin, B, D * H * W)
     y = torch.empty_like(x)
-    _call("pcrl_aug_affine", x, y, inv, flip, vmin, B, D, H, W)
+    call_on_stream("pcrl_aug_affine", x, y, inv, flip, vmin, B, D, H, W)
     return y
 
 
@@ -189,14 +186,14 @@ def apply_intensity(x, sigma, noise_std, gamma, seed, swap_origins=None, patch=(
     S = D * H * W
     a, b = x.contiguous(), torch.empty_like(x)
     for axis in range(3):
-        _call("pcrl_aug_blur_axis", a, b, sigma[axis], B, D, H, W, axis, BLUR_RADIUS)
+        call_on_stream("pcrl_aug_blur_axis", a, b, sigma[axis], B, D, H, W, axis, BLUR_RADIUS)
         a, b = b, (torch.empty_like(x) if axis == 0 else a)      # never write into the caller's tensor
-    _call("pcrl_aug_noise_gamma", a, b, noise_std, gamma, B, S, seed)
+    call_on_stream("pcrl_aug_noise_gamma", a, b, noise_std, gamma, B, S, seed)
     mean, rstd = torch.empty(B, dtype=torch.float32, device=x.device), torch.empty(B, dtype=torch.float32, device=x.device)
-    _call("pcrl_aug_meanstd", b, mean, rstd, B, S)               # a permutation of the voxels leaves mean and std alone
+    call_on_stream("pcrl_aug_meanstd", b, mean, rstd, B, S)               # a permutation of the voxels leaves mean and std alone
     if swap_origins is not None:
-        _call("pcrl_aug_swap", b, swap_origins, B, D, H, W, patch[0], patch[1], patch[2], swap_origins.shape[0])
-    _call("pcrl_aug_znorm", b, a, mean, rstd, B, S)
+        call_on_stream("pcrl_aug_swap", b, swap_origins, B, D, H, W, patch[0], patch[1], patch[2], swap_origins.shape[0])
+    call_on_stream("pcrl_aug_znorm", b, a, mean, rstd, B, S)
     return a
 
 
@@ -691,15 +688,15 @@ def normalise_cubes(c, gen=None, unit=None):
     pre-task's spatial view is drawn and applied in between."""
     if unit is None:
         unit = torch.empty(c.shape, dtype=torch.float32, device=c.device)
-        _call("pcrl_prep_hu_to_unit", c, unit, c.numel())
+        call_on_stream("pcrl_prep_hu_to_unit", c, unit, c.numel())
     B, S = unit.shape[0], unit[0].numel()
     if gen is not None:
         flip, inv = draw_spatial(gen, B, unit.device)
         unit = apply_spatial(unit, flip, inv)
     mean, rstd = torch.empty(B, dtype=torch.float32, device=unit.device), torch.empty(B, dtype=torch.float32, device=unit.device)
     out = torch.empty_like(unit)
-    _call("pcrl_aug_meanstd", unit, mean, rstd, B, S)
-    _call("pcrl_aug_znorm", unit, out, mean, rstd, B, S)
+    call_on_stream("pcrl_aug_meanstd", unit, mean, rstd, B, S)
+    call_on_stream("pcrl_aug_znorm", unit, out, mean, rstd, B, S)
     return out.unsqueeze(1)
 
 

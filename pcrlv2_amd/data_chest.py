@@ -29,6 +29,7 @@ import os
 import numpy as np
 import torch
 
+from ._lib import call_on_stream
 from .data import AugmentedLoader, _LazyLoaders, eval_shard
 
 NPARAM = 40            # PCRL_AUG2D_NPARAM: the per-view record of pcrl_aug2d_* (layout in include/pcrl_hip.h)
@@ -175,23 +176,18 @@ def pack_offsets(rec, src_offsets, sample, S):
 # ---------------------------------------------------------------------------------------------------------------
 # Device side
 # ---------------------------------------------------------------------------------------------------------------
-def _call(name, *args):
-    from ._lib import lib, stream_handle
-    lib().call(name, *args, stream_handle())
-
-
 def apply_views(src, rec_dev, rec_host, S, with_target, u8_out=None):
     """Runs the three kernels over one group of views of side S: src = packed uint8 sources on the device, rec_dev / rec_host = the
     records (int32) on the device and on the host.  -> (out [V,3,S,S] float32, target [V,3,S,S] float32 or None)."""
     V = rec_host.shape[0]
     dev = src.device
     inter = torch.empty(int((rec_host[:, P_CH].astype(np.int64) * S * rec_host[:, P_C]).sum()), dtype=torch.uint8, device=dev)
-    _call("pcrl_aug2d_hresample", src, rec_dev, inter, V, S, int(rec_host[:, P_CH].max()))
+    call_on_stream("pcrl_aug2d_hresample", src, rec_dev, inter, V, S, int(rec_host[:, P_CH].max()))
     view = torch.empty((V, 3, S, S), dtype=torch.uint8, device=dev)
     target = torch.empty((V, 3, S, S), dtype=torch.float32, device=dev) if with_target else None
-    _call("pcrl_aug2d_spatial", inter, rec_dev, view, target, V, S)
+    call_on_stream("pcrl_aug2d_spatial", inter, rec_dev, view, target, V, S)
     out = torch.empty((V, 3, S, S), dtype=torch.float32, device=dev)
-    _call("pcrl_aug2d_photometric", view, rec_dev, out, u8_out, V, S)
+    call_on_stream("pcrl_aug2d_photometric", view, rec_dev, out, u8_out, V, S)
     return out, target
 
 
@@ -456,10 +452,10 @@ def apply_spatial(src, rec_dev, rec_host, S):
     V = rec_host.shape[0]
     dev = src.device
     inter = torch.empty(int((rec_host[:, P_CH].astype(np.int64) * S * rec_host[:, P_C]).sum()), dtype=torch.uint8, device=dev)
-    _call("pcrl_aug2d_hresample", src, rec_dev, inter, V, S, int(rec_host[:, P_CH].max()))
+    call_on_stream("pcrl_aug2d_hresample", src, rec_dev, inter, V, S, int(rec_host[:, P_CH].max()))
     view = torch.empty((V, 3, S, S), dtype=torch.uint8, device=dev)
     target = torch.empty((V, 3, S, S), dtype=torch.float32, device=dev)
-    _call("pcrl_aug2d_spatial", inter, rec_dev, view, target, V, S)
+    call_on_stream("pcrl_aug2d_spatial", inter, rec_dev, view, target, V, S)
     return view, target
 
 

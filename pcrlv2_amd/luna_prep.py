@@ -292,16 +292,12 @@ def build_records(draws):
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------------
-def _call(name, *args):
-    _lib.lib().call(name, *args, _lib.stream_handle())
-
-
 def gpu_resample(vol_dev, spacing, out_xyz):
     """int16 [Z, Y, X] device volume -> int16 [OZ, OY, OX] at 1 mm."""
     Z, Y, X = vol_dev.shape
     ox, oy, oz = out_xyz
     out = torch.empty((oz, oy, ox), dtype=torch.int16, device=vol_dev.device)
-    _call("pcrl_prep_resample", vol_dev, out, X, Y, Z, ox, oy, oz, float(spacing[0]), float(spacing[1]), float(spacing[2]))
+    _lib.call_on_stream("pcrl_prep_resample", vol_dev, out, X, Y, Z, ox, oy, oz, float(spacing[0]), float(spacing[1]), float(spacing[2]))
     return out
 
 
@@ -325,7 +321,7 @@ def gpu_windows(vol_dev, rec, prm, out_elems, ws_elems, max_src, max_cols, padde
     out = torch.empty(out_elems, dtype=torch.float64, device=dev)
     ws = torch.empty(ws_elems, dtype=torch.float64, device=dev)
     stats = torch.empty((W, 3), dtype=torch.int32, device=dev)
-    _call("pcrl_prep_windows", vol_dev, X, Y, Z, rec_d, prm_d, W, int(max_src), int(max_cols), out, out_elems, stats, ws, ws_elems)
+    _lib.call_on_stream("pcrl_prep_windows", vol_dev, X, Y, Z, rec_d, prm_d, W, int(max_src), int(max_cols), out, out_elems, stats, ws, ws_elems)
     return out, stats
 
 

@@ -1646,14 +1646,23 @@ def gn_backward_rows(da, saved, gamma, groups, act, dtype):
 # ----------------------------------------------------------------------------------------------
 # segmentation fine-tuning: out_tr.final_conv + sigmoid + Dice/BCE as one operator (csrc/seg_head.hip)
 # ----------------------------------------------------------------------------------------------
+def _seg_labels(what, labels, numel, device):
+    if labels is not None and (labels.dtype != torch.uint8 or labels.numel() != numel or not labels.is_contiguous() or labels.device != device):
+        raise PcrlError(f"{what}: labels must be a contiguous uint8 bitmask of {numel} voxels on {device}, got {labels.dtype} {tuple(labels.shape)}")
+
+
+def _seg_counts(what, counts, K, device):
+    if counts.dtype != torch.int64 or counts.dim() != 3 or tuple(counts.shape[1:]) != (K, 3) or not counts.is_contiguous() or counts.device != device:
+        raise PcrlError(f"{what}: counts must be a contiguous int64 [cases, {K}, 3] tensor on {device}, got {counts.dtype} {tuple(counts.shape)}")
+
+
 def _seg_args(a, w, b, labels, dtype, what):
     N, D, H, W, C = dims(a)
     K = w.shape[0]
     if a.dtype != dtype or C != 64 or w.numel() != K * 64 or w.dtype != torch.float32 or b.dtype != torch.float32 or b.numel() != K:
         raise PcrlError(f"{what}: activation {a.dtype} with {C} channels against a {tuple(w.shape)} {w.dtype} weight in {dtype} (64 channels are expected)")
     S = D * H * W
-    if labels is not None and (labels.dtype != torch.uint8 or labels.numel() != N * S or not labels.is_contiguous() or labels.device != a.device):
-        raise PcrlError(f"{what}: labels must be a contiguous uint8 bitmask of {N * S} voxels on {a.device}, got {labels.dtype} {tuple(labels.shape)}")
+    _seg_labels(what, labels, N * S, a.device)
     return N, S, K, w.detach().reshape(K, 64).contiguous(), b.detach().contiguous()
 
 
@@ -1692,8 +1701,7 @@ def seg_head_eval(a, w, b, dtype, labels=None, case_index=None, counts=None, wan
     N, S, K, wc, bc = _seg_args(a, w, b, labels, dtype, "seg_head_eval")
     if counts is None:
         counts = torch.zeros((N, K, 3), dtype=torch.int64, device=a.device)
-    if counts.dtype != torch.int64 or counts.dim() != 3 or tuple(counts.shape[1:]) != (K, 3) or not counts.is_contiguous() or counts.device != a.device:
-        raise PcrlError(f"seg_head_eval: counts must be a contiguous int64 [cases, {K}, 3] tensor on {a.device}, got {counts.dtype} {tuple(counts.shape)}")
+    _seg_counts("seg_head_eval", counts, K, a.device)
     if case_index is not None and (case_index.dtype != torch.int32 or case_index.numel() != N or not case_index.is_contiguous() or case_index.device != a.device):
         raise PcrlError(f"seg_head_eval: case_index must be a contiguous int32 [{N}] tensor on {a.device}")
     if case_index is None and counts.shape[0] < N:
@@ -1801,12 +1809,10 @@ def seg_blend(z, starts, weights, shape, labels=None, counts=None, row=0, want_m
     if not 1 <= K <= 7 or min(X, Y, Z) < 1:
         raise PcrlError(f"seg_blend: 1 <= K <= 7 classes and a non-empty volume, got K = {K} and {X} x {Y} x {Z}")
     V = X * Y * Z
-    if labels is not None and (labels.dtype != torch.uint8 or labels.numel() != V or not labels.is_contiguous() or labels.device != dev):
-        raise PcrlError(f"seg_blend: labels must be a contiguous uint8 bitmask of {V} voxels on {dev}, got {labels.dtype} {tuple(labels.shape)}")
+    _seg_labels("seg_blend", labels, V, dev)
     crow = None
     if counts is not None:
-        if counts.dtype != torch.int64 or counts.dim() != 3 or tuple(counts.shape[1:]) != (K, 3) or not counts.is_contiguous() or counts.device != dev:
-            raise PcrlError(f"seg_blend: counts must be a contiguous int64 [cases, {K}, 3] tensor on {dev}, got {counts.dtype} {tuple(counts.shape)}")
+        _seg_counts("seg_blend", counts, K, dev)
         if not 0 <= int(row) < counts.shape[0] or not want_sums:
             raise PcrlError(f"seg_blend: row {row} of a counts table with {counts.shape[0]} rows (counts come with the sums)")
         crow = counts[int(row)]

@@ -289,10 +289,6 @@ def split_of(name, seed, fractions):
 
 
 # ---- GPU --------------------------------------------------------------------------------------------------------------------------
-def _call(name, *args):
-    _lib.lib().call(name, *args, _lib.stream_handle())
-
-
 def _ws(nbytes, device):
     return torch.empty(max(8, int(nbytes)), dtype=torch.uint8, device=device)
 
@@ -309,29 +305,26 @@ def gpu_scan(src):
     """src device [C, Z, Y, X] -> rec int64 device [8] = x0, x1, y0, y1, z0, z1, count, non-finite (half-open box)."""
     C, Z, Y, X = src.shape
     rec = torch.empty(8, dtype=torch.int64, device=src.device)
-    _call("pcrl_segprep_scan", src, src_kind(src), C, X, Y, Z, rec)
+    _lib.call_on_stream("pcrl_segprep_scan", src, src_kind(src), C, X, Y, Z, rec)
     return rec
 
 
 def gpu_stats(src, use_mask, rec=None, clip=None):
     """-> stats float64 device [C, 2] = mean, population std over the mask (use_mask) or every voxel, of the values clipped to clip [C, 2]."""
     C, Z, Y, X = src.shape
-    L = _lib.lib()
     stats = torch.empty((C, 2), dtype=torch.float64, device=src.device)
-    nb = L.fn["pcrl_segprep_stats_ws_bytes"][0](C, X * Y * Z)
-    ws = _ws(nb, src.device)
-    _call("pcrl_segprep_stats", src, src_kind(src), C, X, Y, Z, int(bool(use_mask)), rec, clip, stats, ws, ws.numel())
+    ws = _ws(_lib.lib().call("pcrl_segprep_stats_ws_bytes", C, X * Y * Z), src.device)
+    _lib.call_on_stream("pcrl_segprep_stats", src, src_kind(src), C, X, Y, Z, int(bool(use_mask)), rec, clip, stats, ws, ws.numel())
     return stats
 
 
 def gpu_select(src, ch, use_mask, ranks, out=None):
     """-> float32 device [4]: the order statistics of channel ch at the four 0-based ranks."""
     C, Z, Y, X = src.shape
-    L = _lib.lib()
     if out is None:
         out = torch.empty(4, dtype=torch.float32, device=src.device)
-    ws = _ws(L.fn["pcrl_segprep_select_ws_bytes"][0](), src.device)
-    _call("pcrl_segprep_select", src, src_kind(src), C, ch, X, Y, Z, int(bool(use_mask)), *[int(r) for r in ranks], out, ws, ws.numel())
+    ws = _ws(_lib.lib().call("pcrl_segprep_select_ws_bytes"), src.device)
+    _lib.call_on_stream("pcrl_segprep_select", src, src_kind(src), C, ch, X, Y, Z, int(bool(use_mask)), *[int(r) for r in ranks], out, ws, ws.numel())
     return out
 
 
@@ -349,8 +342,8 @@ def gpu_resample(src, lab, box, out_shape, tab_i, tab_w, stats, clip, region, K,
     """One launch.  box = (x0, y0, z0, NX, NY, NZ); img device [C, OX, OY, OZ] float32 / float16; out_lab device uint8 [OX, OY, OZ]."""
     C, Z, Y, X = src.shape
     OX, OY, OZ = out_shape
-    _call("pcrl_segprep_resample", src, src_kind(src), lab, C, X, Y, Z, *[int(b) for b in box], tab_i, tab_w, stats, clip, region, K,
-          int(bool(use_mask)), img, 1 if img.dtype == torch.float16 else 0, out_lab, OX, OY, OZ)
+    _lib.call_on_stream("pcrl_segprep_resample", src, src_kind(src), lab, C, X, Y, Z, *[int(b) for b in box], tab_i, tab_w, stats, clip, region, K,
+                        int(bool(use_mask)), img, 1 if img.dtype == torch.float16 else 0, out_lab, OX, OY, OZ)
 
 
 def resample_tile(NX, NZ, OX, OZ, use_mask):
@@ -373,7 +366,7 @@ def gpu_restore(pred, tab, box, orig_shape, paint=None):
     PX, PY, PZ = pred.shape
     X, Y, Z = orig_shape
     both = torch.empty((2 if paint is not None else 1, X, Y, Z), dtype=torch.uint8, device=pred.device)
-    _call("pcrl_segprep_restore", pred, PX, PY, PZ, tab, *[int(b) for b in box], paint, both[0], both[1] if paint is not None else None, X, Y, Z)
+    _lib.call_on_stream("pcrl_segprep_restore", pred, PX, PY, PZ, tab, *[int(b) for b in box], paint, both[0], both[1] if paint is not None else None, X, Y, Z)
     return both
 
 

@@ -41,6 +41,7 @@ from . import ops as _ops
 from .loop import to_gpu
 from .models import Segmenter3d
 from .optim import FusedSGD
+from .seg_prep import lerp
 
 
 def dice_from_counts(counts):
@@ -104,27 +105,38 @@ def train_step(model, optimizer, batch):
     return loss.detach(), sums.detach()
 
 
-def evaluate(model, loader, group=None):
-    """One pass of `model.infer` over the tiles of `loader` (data_seg.TileLoader: this rank's cases).  -> {'loss', 'dice': [K], 'mean_dice', 'cases'}"""
+def _held_out(model, n_cases, steps, group, step_sums):
+    """ONE loop.held_out_pass over `steps` (its loader-like object): step_sums(step, counts) runs a step's forward, adds {TP, |pred|, |gt|} into its
+    cases' rows of `counts` int64 [cases, K, 3] and returns the step's float64 sums [4 K + 1].  One all_reduce carries sums and counts, one host
+    read-back follows.  -> {'loss', 'dice': [K], 'mean_dice', 'cases'}"""
     dev = next(model.parameters()).device
-    K, n_cases = model.n_class, len(loader.cases)
+    K = model.n_class
     ns = 4 * K + 1
     counts = torch.zeros((max(n_cases, 1), K, 3), dtype=torch.int64, device=dev)
     acc = torch.zeros(ns + n_cases * K * 3, dtype=torch.float64, device=dev)       # the loss sums, then the counts (< 2^53: exact in float64)
 
-    def per_batch(batch):
-        x = batch[0].to(dev, non_blocking=True).float()
-        _, _, sums, _ = model.infer(x, labels=batch[1].to(dev), case_index=batch[2].to(dev), counts=counts)
-        acc[:ns] += sums
+    def per_step(step):
+        acc[:ns] += step_sums(step, counts)
 
-    def counts_into_acc():       # runs once after the last batch, in front of the all_reduce: ONE collective carries counts and sums
+    def counts_into_acc():       # runs once after the last step, in front of the all_reduce: ONE collective carries counts and sums
         acc[ns:] = counts[:n_cases].reshape(-1).double()
         return acc.new_zeros(0)
 
-    host = _loop.held_out_pass(loader, group, acc, per_batch, also_read=counts_into_acc)
+    host = _loop.held_out_pass(steps, group, acc, per_step, also_read=counts_into_acc)
     table = [[[int(v) for v in host[ns + (c * K + k) * 3:ns + (c * K + k) * 3 + 3]] for k in range(K)] for c in range(n_cases)]
     per, mean = dice_from_counts(table)
     return {"loss": loss_from_sums(host[:ns], K, model.wb, model.wd) if n_cases else float("nan"), "dice": per, "mean_dice": mean, "cases": n_cases}
+
+
+def evaluate(model, loader, group=None):
+    """One pass of `model.infer` over the tiles of `loader` (data_seg.TileLoader: this rank's cases).  -> {'loss', 'dice': [K], 'mean_dice', 'cases'}"""
+    dev = next(model.parameters()).device
+
+    def tile_sums(batch, counts):
+        x = batch[0].to(dev, non_blocking=True).float()
+        return model.infer(x, labels=batch[1].to(dev), case_index=batch[2].to(dev), counts=counts)[2]
+
+    return _held_out(model, len(loader.cases), loader, group, tile_sums)
 
 
 def _fmt(val):
@@ -194,23 +206,10 @@ def evaluate_sliding(model, cases, crop, b, overlap, window, rank=0, world=1, gr
     """`evaluate` with every case predicted by sliding_window: the same dictionary from the same ONE held_out_pass, one all_reduce of sums and counts
     and one host read-back.  The sums of the cases add up (they are sums over counted voxels), so the loss is the pass's, as in `evaluate`.
     `mirror`: sliding_window's mirror codes."""
-    dev = next(model.parameters()).device
-    K, n_cases = model.n_class, len(cases)
-    ns = 4 * K + 1
-    counts = torch.zeros((max(n_cases, 1), K, 3), dtype=torch.int64, device=dev)
-    acc = torch.zeros(ns + n_cases * K * 3, dtype=torch.float64, device=dev)
+    def case_sums(ci, counts):
+        return sliding_window(model, cases[ci], crop, b, overlap, window, counts=counts, row=ci, want_mask=False, mirror=mirror)[2]
 
-    def per_case(ci):
-        acc[:ns] += sliding_window(model, cases[ci], crop, b, overlap, window, counts=counts, row=ci, want_mask=False, mirror=mirror)[2]
-
-    def counts_into_acc():
-        acc[ns:] = counts[:n_cases].reshape(-1).double()
-        return acc.new_zeros(0)
-
-    host = _loop.held_out_pass(_CaseShard(n_cases, rank, world), group, acc, per_case, also_read=counts_into_acc)
-    table = [[[int(v) for v in host[ns + (c * K + k) * 3:ns + (c * K + k) * 3 + 3]] for k in range(K)] for c in range(n_cases)]
-    per, mean = dice_from_counts(table)
-    return {"loss": loss_from_sums(host[:ns], K, model.wb, model.wd) if n_cases else float("nan"), "dice": per, "mean_dice": mean, "cases": n_cases}
+    return _held_out(model, len(cases), _CaseShard(len(cases), rank, world), group, case_sums)
 
 
 def resume_segmenter(path, model, optimizer, rank):
@@ -479,12 +478,6 @@ def postprocess(args, log=print):
 SURFACE_KEYS = ("hd95", "hd", "assd")
 
 
-def _lerp(a, b, t):
-    """numpy's linear interpolation between two neighbouring order statistics (numpy.lib._function_base_impl._lerp), one float64 operation at a time."""
-    d = b - a
-    return b - d * (1.0 - t) if t >= 0.5 else a + d * t
-
-
 def surface_from_records(records, q=0.95):
     """Host, float64: the records of ops.surf_dist_stats, int64 [K][8] -> {'hd95', 'hd', 'assd': float64 [K], 'n_pred', 'n_gt': int64 [K]}.
     hd95 is numpy.percentile(U, 100 q) with the default linear method on the distances U = sqrt(d2) (sqrt is monotone, so the order statistics of
@@ -507,7 +500,7 @@ def surface_from_records(records, q=0.95):
         virtual = np.float64(q) * np.float64(n - 1)
         lo = np.floor(virtual)
         d_lo, d_hi, d_max = (np.sqrt(as_f[k, 3 + i]) for i in range(3))
-        out["hd95"][k] = d_lo if virtual >= n - 1 else _lerp(d_lo, d_hi, virtual - lo)
+        out["hd95"][k] = d_lo if virtual >= n - 1 else lerp(d_lo, d_hi, virtual - lo)
         out["hd"][k] = d_max
         out["assd"][k] = (as_f[k, 6] / na + as_f[k, 7] / nb) / 2.0
     return out

@@ -190,12 +190,14 @@ def _select_case(values, ranks):
     return a
 
 
-@pytest.mark.parametrize("name", ["n1", "n2", "n3", "n4097", "constant", "ties", "negatives", "zeros"])
+@pytest.mark.parametrize("name", ["n1", "n2", "n3", "n4097", "constant", "ties", "negatives", "zeros", "last_byte"])
 def test_select_and_percentiles_bit_for_bit(name):
     rng = np.random.default_rng(9)
     values = {"n1": [2.5], "n2": [3.0, -1.0], "n3": [0.5, 0.25, 8.0], "n4097": rng.standard_normal(4097) * 100, "constant": [1.75] * 300,
               "ties": np.repeat([-2.0, 0.5, 0.5, 0.5, 3.0], 40), "negatives": -np.abs(rng.standard_normal(777)) - 1e-3,
-              "zeros": rng.permutation(np.array([0.0] * 30 + [-0.0] * 30 + [-1e-30, 1e-30, -5.0, 5.0], dtype=np.float32))}[name]
+              "zeros": rng.permutation(np.array([0.0] * 30 + [-0.0] * 30 + [-1e-30, 1e-30, -5.0, 5.0], dtype=np.float32)),
+              # 257 keys (more than one block) that agree in their three leading bytes: only the last pass tells them apart, under one full prefix
+              "last_byte": (np.uint32(0x42280000) + (np.arange(257, dtype=np.uint32) * np.uint32(37)) % np.uint32(256)).view(np.float32)}[name]
     v = np.asarray(values, dtype=np.float32)
     n = v.size
     for q_lo, q_hi in ((0.5, 99.5), (0.0, 100.0), (40.0, 60.0)):

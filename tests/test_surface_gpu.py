@@ -216,6 +216,16 @@ def test_two_values_one_value_and_none():
     assert rec.tolist() == [1, 0, 77, 77, 77, 77, 77, 77]
     rec = ops.surf_dist_stats(_dev(d2a), _dev(mb * 0), _dev(d2b), _dev(mb * 0), 0).cpu().numpy()
     assert not rec.any()
+    # 257 keys (more than one block) that agree in their seven leading bytes: only the last pass tells them apart, under one full prefix;
+    # q = 0: ranks 0, 1 and n - 1 in one call; q = 1: all three ranks n - 1
+    last = (np.uint64(0x4024000000000000) + (np.arange(257, dtype=np.uint64) * np.uint64(37)) % np.uint64(256)).view(np.float64).reshape(1, 1, 257)
+    on, third, back = np.ones(last.shape, np.uint8), (np.arange(257) % 3 == 0).astype(np.uint8).reshape(last.shape), last[:, :, ::-1].copy()
+    for q in (0.0, 1.0):
+        for m_b in (third, on):      # the keys of one side and a third of the other's; every key twice
+            st = R.stats(last, on.astype(bool), back, m_b.astype(bool), q)
+            rec = ops.surf_dist_stats(_dev(last), _dev(on), _dev(back), _dev(m_b), 0, q).cpu().numpy()
+            _check_record(rec, st, f"last byte q={q} n_b={int(m_b.sum())}")
+            assert st["d2"][2] == last.max() and st["d2"][0] == (last.max() if q else last.min())
 
 
 # ---- the chain and surface_metrics -----------------------------------------------------------------------------------------------------
