@@ -16,23 +16,27 @@ namespace {
 constexpr int GN_TILE_ROWS = 512;
 
 // partial[((n * tiles + tile) * C + c) * 2 + {0,1}] = (sum, sum^2) of y[n][rows of the tile][c]; thread = channel vector x row slot
+// The sums of a tile are taken in float64 and rounded ONCE to the float32 partial: a thread adds up to 512 rows serially, and a float32
+// running sum of squares of a group whose mean is many standard deviations (var = E[y^2] - mean^2 cancels in gn_finalize_kernel) cost
+// rstd 4.6e-3 relative at mean / std = 100, twice what torch's float32 sums lose and 13 x BatchNorm's per-tile partials
+// (tests/test_variants_edges_gpu.py); with one rounding per tile it is 8.6e-4.  Memory-bound either way: two float64 operations per element.
 template <typename T>
 __global__ void __launch_bounds__(256) gn_stats_kernel(const T* __restrict__ y, float* __restrict__ partial, int64_t S, int C) {
   constexpr int VEC = 16 / (int)sizeof(T);
-  extern __shared__ __attribute__((aligned(16))) float sm[];   // [slots][C][2]
+  extern __shared__ __attribute__((aligned(16))) double sm[];   // [slots][C][2]
   const int tid = threadIdx.x, nvec = C / VEC;
   const int cv = tid % nvec, slot = tid / nvec, nslots = 256 / nvec;
   const T* base = y + (int64_t)blockIdx.y * S * C;
   const int64_t rbeg = (int64_t)blockIdx.x * GN_TILE_ROWS;
   const int64_t rend = (rbeg + GN_TILE_ROWS < S) ? rbeg + GN_TILE_ROWS : S;
-  float s1[VEC], s2[VEC];
+  double s1[VEC], s2[VEC];
 #pragma unroll
-  for (int j = 0; j < VEC; ++j) s1[j] = s2[j] = 0.f;
+  for (int j = 0; j < VEC; ++j) s1[j] = s2[j] = 0.0;
   for (int64_t r = rbeg + slot; r < rend; r += nslots) {
     const Vec16<T> x = ld16(base + (r * nvec + cv) * VEC);
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-      const float v = to_f(x.v[j]);
+      const double v = (double)to_f(x.v[j]);
       s1[j] += v;
       s2[j] += v * v;
     }
@@ -44,14 +48,14 @@ __global__ void __launch_bounds__(256) gn_stats_kernel(const T* __restrict__ y, 
   }
   __syncthreads();
   for (int c = tid; c < C; c += 256) {
-    float a = 0.f, b = 0.f;
+    double a = 0.0, b = 0.0;
     for (int q = 0; q < nslots; ++q) {
       a += sm[(q * C + c) * 2 + 0];
       b += sm[(q * C + c) * 2 + 1];
     }
     float* o = partial + (((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * C + c) * 2;
-    o[0] = a;
-    o[1] = b;
+    o[0] = (float)a;
+    o[1] = (float)b;
   }
 }
 
@@ -153,7 +157,7 @@ extern "C" int pcrl_gn_stats(const void* y, float* partial, int N, int64_t S, in
   const int vec = dtype == PCRL_BF16 ? 8 : 4;
   PCRL_REQUIRE(C > 0 && C % vec == 0 && (C / vec) <= 256 && 256 % (C / vec) == 0, "gn_stats: C=%d: channel vectors must divide 256", C);
   const dim3 grid((unsigned)pcrl_gn_stats_tiles(S), (unsigned)N);
-  const size_t lds = (size_t)(256 / (C / vec)) * C * 2 * sizeof(float);
+  const size_t lds = (size_t)(256 / (C / vec)) * C * 2 * sizeof(double);   // 16 KB float32, 32 KB bf16
   if (dtype == PCRL_BF16) hipLaunchKernelGGL(gn_stats_kernel<bf16>, grid, dim3(256), lds, as_stream(stream), (const bf16*)y, partial, S, C);
   else hipLaunchKernelGGL(gn_stats_kernel<float>, grid, dim3(256), lds, as_stream(stream), (const float*)y, partial, S, C);
   return pcrl_check_launch("gn_stats");
