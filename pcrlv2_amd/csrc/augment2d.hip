@@ -3,7 +3,8 @@
 // transform of that chain hands its arithmetic to Pillow, so each kernel restates Pillow's integer / float arithmetic exactly:
 //
 //   RandomResizedCrop (crop + BILINEAR resize: Pillow's two-pass fixed-point resampler, horizontal pass first)
-//       -> pcrl_aug2d_hresample (horizontal pass of the crop box into a uint8 intermediate)
+//       -> pcrl_aug2d_hresample (horizontal pass of the crop box into a uint8 intermediate).  Pillow itself runs the vertical pass first on a
+//          crop more than 100 times as tall as wide: exact for crops up to 100 : 1 (the drawn ones are 3/4 .. 4/3)
 //   RandomRotation (NEAREST, 16.16 fixed-point affine, fill 0) + RandomHorizontalFlip
 //       -> pcrl_aug2d_spatial (the vertical pass evaluated only at the resized pixel the rotation and the flip pick; writes the uint8 view
 //          and, for the global views, the float32 target Normalize(ToTensor(view)))
