@@ -825,6 +825,57 @@ int pcrl_seg_blend(const float* z, int64_t P, const int* sx, const int* sy, cons
                    int64_t* counts, double* sums, float* loss, float wb, float wd, void* ws, size_t ws_bytes, pcrl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * 3D path, segmentation fine-tuning with a SOFTMAX head over mutually exclusive classes (csrc/seg_head_mc.hip): the sibling of pcrl_seg_head_*.
+ *   a, w, b, dtype, N, S as there; 2 <= K <= 16 classes, the background (class 0) included.  labels uint8 [N * S] is a LABEL MAP: y = byte & 0x7F is the
+ *   voxel's class index, bit 7 = the voxel is NOT counted (no sum, zero gradient).  The range of y is not checked on the device (the host checks a case when
+ *   it opens it): a voxel with y >= K is treated as not counted by every entry point.
+ *   Per voxel, in one fixed order shared by all four kernels (the file header states the tree of every sum):
+ *       z_k = b_k + sum_c W[k][c] a[c];  m = max_k z_k;  e_k = exp(z_k - m);  s = sum_k e_k;  p_k = e_k / s;  ce = (m - z_y) + log s
+ *   forward : sums float64 [4 K + 1] = {I_k = sum_{y=k} p_k, P_k = sum p_k, G_k = #{y = k}, CE_k = sum_{y=k} ce} per class over the counted voxels, then Mc;
+ *             loss float32 [1] = wc (sum_k CE_k) / Mc + wd (1 - (1 / (K-1)) sum_{k=1}^{K-1} (2 I_k + 1) / (P_k + G_k + 1)): the background is not in the Dice
+ *             mean; Mc = 0: the CE term is 0 and so is the loss.  One read of a, per-block float64 partials, a fixed-order second launch; no
+ *             floating-point atomics and no [M][K] tensor.
+ *   backward: from dloss[0] = c and the forward's sums (both on the device).  q_0 = 0, q_k = -(c wd / (K-1)) (2 [y=k] / U_k - (2 I_k + 1) / U_k^2),
+ *             U_k = P_k + G_k + 1:   dz_j = (c wc / Mc) (p_j - [y=j]) + p_j (q_j - sum_k p_k q_k).
+ *             dx `dtype` [N * S][64] written once (NULL: not wanted; rows of uncounted voxels are exactly zero, and their activations, finite or not, enter
+ *             nothing); dw float32 [K][64], db float32 [K] from per-block partials added in block order.
+ *   eval    : the forward (labels may be NULL: every voxel counted as background) plus counts[case_index[n]][k] += {TP, |pred|, |gt|} (int64
+ *             [n_cases][K][3], ALL K rows, NOT cleared here; 64-bit integer atomics) with pred = the LOWEST k with z_k == m; case_index int32 [N] or NULL
+ *             (= n), an index outside [0, n_cases) is skipped; labelmap uint8 [N * S] or NULL: the predicted class index, 0 where the voxel is not counted.
+ *   logits  : z float32 [N * S][K], each bit-identical to the logit eval takes its maximum over, stored as pcrl_seg_head_logits_acc stores: at the
+ *             un-mirrored voxel s' of the sample grid cx x cy x cz (S = cx * cy * cz), v = first ? z_k : z[s'][k] + z_k; z[s'][k] = v * scale (plain float32,
+ *             one add, one multiply).  flip = 0, first = 1, scale = 1 is the plain case.  One thread reads and writes each element; no workspace.
+ *   ws: pcrl_seg_mc_head_ws_bytes(N, S, K) bytes for fwd / bwd / eval (0 for sizes the entry points refuse).
+ *   PCRL_EINVAL for K outside 2..16 and whatever the pcrl_seg_head_* siblings refuse.
+ * pcrl_seg_labelmap_to_bits / _keep -- label maps through the bitmask tools (surface distances, connected components), a group of n <= 7 classes
+ *   first .. first + n - 1 at a time, `count` bytes:  to_bits: out bit j = ((lab & 0x7F) == first + j), bit 7 carried over;
+ *   keep: out = lab, except that a voxel whose class is in the group and whose bit in `bits` is clear becomes background (bit 7 carried over).  out may be lab. */
+size_t pcrl_seg_mc_head_ws_bytes(int N, int64_t S, int K);
+int pcrl_seg_mc_head_fwd(const void* a, const float* w, const float* b, const uint8_t* labels, double* sums, float* loss, float wc, float wd, void* ws,
+                         size_t ws_bytes, int N, int64_t S, int K, int dtype, pcrl_stream_t stream);
+int pcrl_seg_mc_head_bwd(const void* a, const float* w, const float* b, const uint8_t* labels, const double* sums, const float* dloss, float wc, float wd,
+                         void* dx, float* dw, float* db, void* ws, size_t ws_bytes, int N, int64_t S, int K, int dtype, pcrl_stream_t stream);
+int pcrl_seg_mc_head_eval(const void* a, const float* w, const float* b, const uint8_t* labels, const int* case_index, int64_t* counts, int n_cases,
+                          uint8_t* labelmap, double* sums, float* loss, float wc, float wd, void* ws, size_t ws_bytes, int N, int64_t S, int K, int dtype,
+                          pcrl_stream_t stream);
+int pcrl_seg_mc_head_logits(const void* a, const float* w, const float* b, float* z, int N, int64_t S, int K, int dtype, int cx, int cy, int cz, int flip,
+                            int first, float scale, pcrl_stream_t stream);
+/* pcrl_seg_mc_blend -- pcrl_seg_blend's label-map sibling (csrc/seg_blend.hip): the same inputs and the same per-voxel accumulation (w = (wx wy) wz;
+ *   num_k += w z_k; den += w; plain float32, covering patches in ascending ix, iy, iz), 2 <= K <= 16.  Outputs, each may be NULL:
+ *     labelmap uint8 [X][Y][Z]: the LOWEST k with maximal num_k (no division decides a prediction); 0 where the voxel is not counted
+ *     probs  float32 [K][X][Y][Z]: softmax of zbar_k = num_k / den (m = max, e_k = exp(zbar_k - m), s summed in ascending k, e_k / s)
+ *     numden float32 [2 K + 1][X][Y][Z]: num_k per class, then den, then zbar_k per class (tests)
+ *     sums float64 [4 K + 1] and loss float32 [1] (both or neither): the softmax head's formula on zbar; ws: pcrl_seg_mc_blend_ws_bytes
+ *     counts int64 [K][3] (with sums only): {TP, |pred|, |gt|} of all K classes ADDED to this one row (integer atomics)
+ *   No floating-point atomics: two runs give identical bytes.  PCRL_EINVAL for K outside 2..16 and whatever pcrl_seg_blend refuses. */
+size_t pcrl_seg_mc_blend_ws_bytes(int X, int Y, int Z);
+int pcrl_seg_mc_blend(const float* z, int64_t P, const int* sx, const int* sy, const int* sz, int nx, int ny, int nz, const float* wx, const float* wy,
+                      const float* wz, int cx, int cy, int cz, int X, int Y, int Z, int K, const uint8_t* labels, uint8_t* labelmap, float* probs,
+                      float* numden, int64_t* counts, double* sums, float* loss, float wc, float wd, void* ws, size_t ws_bytes, pcrl_stream_t stream);
+int pcrl_seg_labelmap_to_bits(const uint8_t* lab, int first, int n, uint8_t* out, int64_t count, pcrl_stream_t stream);
+int pcrl_seg_labelmap_keep(const uint8_t* lab, const uint8_t* bits, int first, int n, uint8_t* out, int64_t count, pcrl_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * 3D path, surface-distance metrics of stored segmentation masks: HD95, HD, ASSD (csrc/surface_dist.hip, compiled with -ffp-contract=off).
  *   Masks are the uint8 bitmasks of the segmenter, [X][Y][Z]: bit k = class k, bit 7 of the GROUND TRUTH = the voxel is not counted and belongs to
  *   neither mask.  The definitions are MedPy's hd95 / hd / assd; the host finishes them in float64 (train_seg.surface_metrics).

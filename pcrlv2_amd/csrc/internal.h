@@ -125,6 +125,50 @@ int pcrl_weighted_colsum(const void* v, const float* rowscale, float* out, void*
 // partial [nb][32] float64 per-block sums (slot k * 4 + {I, P, G, BCE}, slot 28: counted voxels) -> sums [4 K + 1] and loss [1], added in block order
 constexpr int PCRL_SEG_SLOTS = 32, PCRL_SEG_CNT_SLOT = 28;
 void pcrl_seg_sums_launch(const double* partial, int nb, int K, float wb, float wd, double* sums, float* loss, hipStream_t stream);
+// ---- seg_head.hip / seg_head_mc.hip: what the sigmoid head and the softmax head (label maps) share ----------------------------------------
+// The launch geometry, the prefetching row fetch, the per-`sub` wave sum, the un-mirroring index of the accumulating logits kernels and the
+// second launch of the weight gradient.  partial [nb][K * 65] float32 per-block dW [K][64] + db [K] -> dw, db, added in block order.
+constexpr int PCRL_SEG_C = 64, PCRL_SEG_MAX_BLOCKS = 1024;
+__host__ __device__ inline int pcrl_seg_wstride(int K) { return K * (PCRL_SEG_C + 1); }   // floats of one block's dW [K][64] + db [K] partial
+void pcrl_seg_wsum_launch(const float* partial, int nb, int K, float* dw, float* db, hipStream_t stream);
+
+// blocks per sample: enough to fill the device, few enough that the second launches stay short; a function of the sizes only (determinism)
+inline int sh_gx(int N, int64_t S) {
+  const int64_t want = (S + 31) / 32, cap = PCRL_SEG_MAX_BLOCKS / N > 0 ? PCRL_SEG_MAX_BLOCKS / N : 1;
+  return (int)(want < cap ? want : cap);
+}
+
+template <typename T>
+__device__ __forceinline__ void sh_fetch(const T* __restrict__ a, const uint8_t* __restrict__ labels, int64_t base, int s, int S, int sub, Vec16<T>& x,
+                                         unsigned& lab) {
+  constexpr int V = Vec16<T>::N;
+  if (s < S) {
+    x = ld16(a + (base + s) * PCRL_SEG_C + sub * V);
+    lab = labels ? labels[base + s] : 0u;
+  } else {      // past the sample's end: a zero row that is not counted
+#pragma unroll
+    for (int j = 0; j < V; ++j) x.v[j] = from_f<T>(0.0f);
+    lab = 0x80u;
+  }
+}
+
+// sum over the lanes of a wave that own the same `sub` (one per voxel group)
+template <int LPV, typename A> __device__ __forceinline__ A sh_group_sum(A v) {
+#pragma unroll
+  for (int o = 32; o >= LPV; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+struct ShMirror {
+  int cx, cy, cz, flip;      // the sample's grid (S = cx * cy * cz, z fastest) and the mirror code: bit 0 = x, bit 1 = y, bit 2 = z
+};
+
+// float index in z of class `sub` at the un-mirrored voxel of (i, j, k) of the sample that starts at voxel `base`
+__device__ __forceinline__ int64_t sh_unmirrored(const ShMirror& m, int64_t base, int i, int j, int k, int K, int sub) {
+  const int ii = (m.flip & 1) ? m.cx - 1 - i : i, jj = (m.flip & 2) ? m.cy - 1 - j : j, kk = (m.flip & 4) ? m.cz - 1 - k : k;
+  return (base + ((int64_t)ii * m.cy + jj) * m.cz + kk) * K + sub;
+}
+
 // The probability of a logit: the blend's loss equals the head's only because both use this one expression.
 __device__ __forceinline__ float seg_sigmoid(float z) { return 1.0f / (1.0f + expf(-z)); }
 // CALL(KK) with the compile-time class count KK = K; the entry points have checked 1 <= K <= 7.
@@ -138,3 +182,28 @@ __device__ __forceinline__ float seg_sigmoid(float z) { return 1.0f / (1.0f + ex
     case 6: CALL(6); break;                  \
     default: CALL(7); break;                 \
   }
+
+// ---- seg_head_mc.hip: the softmax head's fixed-order second launch, shared with seg_blend.hip's label-map blend ------------------------------
+// partial [nb][72] float64 per-block sums (slot k * 4 + {I, P, G, CE}, slot 4 K: counted voxels) -> sums [4 K + 1] and loss [1], added in block order
+constexpr int PCRL_SEG_MC_SLOTS = 72;
+void pcrl_seg_mc_sums_launch(const double* partial, int nb, int K, float wc, float wd, double* sums, float* loss, hipStream_t stream);
+// CALL(KK) with the compile-time class count KK = K; the entry points have checked 2 <= K <= 16.
+#define PCRL_SEG_MC_DISPATCH_K(CALL) \
+  switch (K) {                       \
+    case 2: CALL(2); break;          \
+    case 3: CALL(3); break;          \
+    case 4: CALL(4); break;          \
+    case 5: CALL(5); break;          \
+    case 6: CALL(6); break;          \
+    case 7: CALL(7); break;          \
+    case 8: CALL(8); break;          \
+    case 9: CALL(9); break;          \
+    case 10: CALL(10); break;        \
+    case 11: CALL(11); break;        \
+    case 12: CALL(12); break;        \
+    case 13: CALL(13); break;        \
+    case 14: CALL(14); break;        \
+    case 15: CALL(15); break;        \
+    default: CALL(16); break;        \
+  }
+

@@ -37,17 +37,11 @@
 
 namespace {
 
-constexpr int SH_THREADS = 256, SH_C = 64, SH_MAX_K = 7, SH_MAX_BLOCKS = 1024, SH_SLOTS = 32, SH_CNT = 28, SH_SLICES = 8;
+constexpr int SH_THREADS = 256, SH_C = PCRL_SEG_C, SH_MAX_K = 7, SH_SLOTS = 32, SH_CNT = 28, SH_SLICES = 8;
 constexpr float SH_EPS = 1.0f;
 static_assert(SH_SLOTS == PCRL_SEG_SLOTS && SH_CNT == PCRL_SEG_CNT_SLOT, "seg_blend.hip writes its partials in this layout");
 
-__host__ __device__ inline int sh_wstride(int K) { return K * (SH_C + 1); }   // floats of one block's dW [K][64] + db [K] partial
-
-// blocks per sample: enough to fill the device, few enough that the second launches stay short; a function of the sizes only (determinism)
-inline int sh_gx(int N, int64_t S) {
-  const int64_t want = (S + 31) / 32, cap = SH_MAX_BLOCKS / N > 0 ? SH_MAX_BLOCKS / N : 1;
-  return (int)(want < cap ? want : cap);
-}
+__host__ __device__ inline int sh_wstride(int K) { return pcrl_seg_wstride(K); }
 
 template <typename T, int K>
 __device__ __forceinline__ void sh_load_w(const float* __restrict__ W, int sub, float (&w)[K][Vec16<T>::N]) {
@@ -74,27 +68,6 @@ __device__ __forceinline__ float sh_logit(const Vec16<T>& x, const float (&w)[K]
     if (sub == k) z = d;
   }
   return z + bk;
-}
-
-template <typename T>
-__device__ __forceinline__ void sh_fetch(const T* __restrict__ a, const uint8_t* __restrict__ labels, int64_t base, int s, int S, int sub, Vec16<T>& x,
-                                         unsigned& lab) {
-  constexpr int V = Vec16<T>::N;
-  if (s < S) {
-    x = ld16(a + (base + s) * SH_C + sub * V);
-    lab = labels ? labels[base + s] : 0u;
-  } else {      // past the sample's end: a zero row that is not counted
-#pragma unroll
-    for (int j = 0; j < V; ++j) x.v[j] = from_f<T>(0.0f);
-    lab = 0x80u;
-  }
-}
-
-// sum over the lanes of a wave that own the same `sub` (one per voxel group)
-template <int LPV, typename A> __device__ __forceinline__ A sh_group_sum(A v) {
-#pragma unroll
-  for (int o = 32; o >= LPV; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // grid = (gx, N); block = 256.  partial[block][SH_SLOTS] float64: slot k * 4 + {0: I, 1: P, 2: G, 3: BCE}, slot SH_CNT: counted voxels.
@@ -355,16 +328,6 @@ __global__ void __launch_bounds__(SH_THREADS) seg_head_logits_kernel(const T* __
   }
 }
 
-struct ShMirror {
-  int cx, cy, cz, flip;      // the sample's grid (S = cx * cy * cz, z fastest) and the mirror code: bit 0 = x, bit 1 = y, bit 2 = z
-};
-
-// float index in z of class `sub` at the un-mirrored voxel of (i, j, k) of the sample that starts at voxel `base`
-__device__ __forceinline__ int64_t sh_unmirrored(const ShMirror& m, int64_t base, int i, int j, int k, int K, int sub) {
-  const int ii = (m.flip & 1) ? m.cx - 1 - i : i, jj = (m.flip & 2) ? m.cy - 1 - j : j, kk = (m.flip & 4) ? m.cz - 1 - k : k;
-  return (base + ((int64_t)ii * m.cy + jj) * m.cz + kk) * K + sub;
-}
-
 // grid = (gx, N); block = 256.  The logits kernel with an un-mirroring, accumulating store: lane sub < K of voxel s = (i, j, k) owns z[n][s'][sub] at the
 // un-mirrored voxel s', reads it (unless FIRST), adds its logit and stores the sum times `scale`.  s -> s' is a bijection of the sample's voxels, so
 // every element of z is read and written by this one lane of the call.  (i, j, k) is divided out once and then advanced by the block stride with carries.
@@ -482,6 +445,10 @@ void pcrl_seg_sums_launch(const double* partial, int nb, int K, float wb, float 
   hipLaunchKernelGGL(seg_head_sums_kernel, dim3(1), dim3(SH_THREADS), 0, stream, partial, nb, K, wb, wd, sums, loss);
 }
 
+void pcrl_seg_wsum_launch(const float* partial, int nb, int K, float* dw, float* db, hipStream_t stream) {
+  hipLaunchKernelGGL(seg_head_wsum_kernel, dim3((sh_wstride(K) + 63) / 64), dim3(SH_THREADS), 0, stream, partial, nb, K, dw, db);
+}
+
 extern "C" int pcrl_seg_head_logits(const void* a, const float* w, const float* b, float* z, int N, int64_t S, int K, int dtype, pcrl_stream_t stream) {
   if (int rc = seg_head_check("seg_head_logits", N, S, K, dtype)) return rc;
   PCRL_REQUIRE(a && w && b && z, "seg_head_logits: null pointer");
@@ -546,6 +513,6 @@ extern "C" int pcrl_seg_head_bwd(const void* a, const float* w, const float* b, 
   else seg_head_launch_bwd<float, KK>(grid, st, a, w, b, labels, sums, dloss, wb, wd, dx, partial, (int)S)
   PCRL_SEG_DISPATCH_K(SH_BWD)
 #undef SH_BWD
-  hipLaunchKernelGGL(seg_head_wsum_kernel, dim3((sh_wstride(K) + 63) / 64), dim3(SH_THREADS), 0, st, partial, gx * N, K, dw, db);
+  pcrl_seg_wsum_launch(partial, gx * N, K, dw, db, st);
   return pcrl_check_launch("seg_head_bwd");
 }

@@ -19,6 +19,10 @@ zoom, flips and per-channel intensity parameters and cuts a source box around th
 the device (ops.seg_augment, csrc/seg_augment.hip) by train_seg.train_step.  Without `aug` nothing changes.
 
 Mirror test-time augmentation (parse_mirror, mirror_letters): the mirror codes train_seg.sliding_window shows every patch in.
+
+Label maps (head='softmax'): a label byte holds the class index in bits 0..6 (0 = background) and 'not counted' in bit 7, so cut,
+cut_tile, cut_box and the augmentation carry it unchanged.  check_n_class(n, head) takes 2..16 for it, open_case(head='softmax') refuses a class index
+>= n_class naming the file and the value, synthetic_case(head='softmax') draws DISJOINT phantoms as class indices; Case.foreground is "non-background".
 """
 from __future__ import annotations
 
@@ -42,7 +46,22 @@ def parse_crop(crop):
     return c
 
 
-def check_n_class(n_class):
+HEADS = ("sigmoid", "softmax")
+
+
+def check_head(head):
+    if head not in HEADS:
+        raise SystemExit(f"--head {head}: 'sigmoid' (overlapping regions, labels are bitmasks; the default) or 'softmax' (mutually exclusive classes, "
+                         "labels are label maps)")
+    return head
+
+
+def check_n_class(n_class, head="sigmoid"):
+    if check_head(head) == "softmax":
+        if not 2 <= int(n_class) <= 16:
+            raise SystemExit(f"--n_class {n_class}: 2..16 with --head softmax (mutually exclusive classes, the background counted; a label byte holds "
+                             "the class index in bits 0..6, bit 7 means 'not counted')")
+        return int(n_class)
     if not 1 <= int(n_class) <= 7:
         raise SystemExit(f"--n_class {n_class}: 1..7 (one bit of the label byte per class; bit 7 means 'not counted')")
     return int(n_class)
@@ -73,7 +92,7 @@ def read_list(data_dir, list_file):
         return [ln.strip() for ln in f if ln.strip()]
 
 
-def open_case(data_dir, name, n_class, in_channels, need_seg=True):
+def open_case(data_dir, name, n_class, in_channels, need_seg=True, head="sigmoid"):
     img_path, seg_path = os.path.join(data_dir, name + "_img.npy"), os.path.join(data_dir, name + "_seg.npy")
     if not os.path.exists(img_path):
         raise SystemExit(f"{img_path}: missing (a case is <case>_img.npy [C,X,Y,Z] float32 / float16 and <case>_seg.npy [X,Y,Z] uint8)")
@@ -87,6 +106,12 @@ def open_case(data_dir, name, n_class, in_channels, need_seg=True):
         seg = np.load(seg_path, mmap_mode="r")
         if seg.dtype != np.uint8 or tuple(seg.shape) != tuple(img.shape[1:]):
             raise SystemExit(f"{seg_path}: expected a uint8 bitmask of shape {tuple(img.shape[1:])}, got {seg.dtype} {seg.shape}")
+        if head == "softmax":       # a label map: the class index in bits 0..6
+            top = int((np.asarray(seg).reshape(-1) & 0x7F).max()) if seg.size else 0
+            if top >= n_class:
+                raise SystemExit(f"{seg_path}: label value {top} but --n_class is {n_class} with --head softmax (a label-map byte holds the class index "
+                                 f"0..{n_class - 1} in bits 0..6, 0 = background; only bit 7, 'not counted', may be set above it)")
+            return Case(name, img, seg)
         bits = int(np.bitwise_or.reduce(np.asarray(seg).reshape(-1))) if seg.size else 0
         bad = bits & 0x7F & ~((1 << n_class) - 1)
         if bad:
@@ -95,8 +120,8 @@ def open_case(data_dir, name, n_class, in_channels, need_seg=True):
     return Case(name, img, seg)
 
 
-def open_cases(data_dir, list_file, n_class, in_channels, need_seg=True):
-    return [open_case(data_dir, n, n_class, in_channels, need_seg) for n in read_list(data_dir, list_file)]
+def open_cases(data_dir, list_file, n_class, in_channels, need_seg=True, head="sigmoid"):
+    return [open_case(data_dir, n, n_class, in_channels, need_seg, head) for n in read_list(data_dir, list_file)]
 
 
 # ---- cutting ----------------------------------------------------------------------------------------------------------------------
@@ -515,11 +540,26 @@ class TileLoader:
 
 
 # ---- synthetic phantoms -----------------------------------------------------------------------------------------------------------
-def synthetic_case(seed, index, shape, n_class, in_channels=1):
+def synthetic_case(seed, index, shape, n_class, in_channels=1, head="sigmoid"):
     """A phantom, a fixed function of (seed, index): unit noise; class k is an ellipsoid (the K of them overlap: each is drawn around the first one's
-    centre) inside which every channel is raised by 1.5 (k + 1).  -> Case with in-memory arrays."""
+    centre) inside which every channel is raised by 1.5 (k + 1).  -> Case with in-memory arrays.
+    head='softmax': a LABEL MAP of n_class classes, the background (0) included -- the classes 1..n_class-1 are DISJOINT ellipsoids, one per slab of
+    the first axis, inside which every channel is raised by 1.5 k."""
     rng = np.random.default_rng([int(seed), int(index)])
     shape = tuple(int(s) for s in shape)
+    if head == "softmax":
+        img = rng.standard_normal((in_channels,) + shape, dtype=np.float32)
+        seg = np.zeros(shape, dtype=np.uint8)
+        grid = np.meshgrid(*[np.arange(n, dtype=np.float32) for n in shape], indexing="ij")
+        slab = shape[0] / float(n_class - 1)
+        for k in range(1, n_class):
+            lo = (k - 1) * slab
+            centre = np.array([lo + rng.uniform(0.4, 0.6) * slab, rng.uniform(0.35, 0.65) * shape[1], rng.uniform(0.35, 0.65) * shape[2]])
+            radii = np.array([rng.uniform(0.3, 0.5) * slab, rng.uniform(0.15, 0.3) * shape[1], rng.uniform(0.15, 0.3) * shape[2]])
+            inside = (sum(((g - c) / r) ** 2 for g, c, r in zip(grid, centre, radii)) <= 1.0) & (grid[0] >= lo) & (grid[0] < lo + slab)
+            seg[inside] = np.uint8(k)
+            img[:, inside] += np.float32(1.5 * k)
+        return Case("phantom%03d" % index, img, seg)
     img = rng.standard_normal((in_channels,) + shape, dtype=np.float32)
     seg = np.zeros(shape, dtype=np.uint8)
     grid = np.meshgrid(*[np.arange(n, dtype=np.float32) for n in shape], indexing="ij")
@@ -533,11 +573,11 @@ def synthetic_case(seed, index, shape, n_class, in_channels=1):
     return Case("phantom%03d" % index, img, seg)
 
 
-def write_synthetic(data_dir, names, shape, n_class, in_channels=1, seed=0, first_index=0):
+def write_synthetic(data_dir, names, shape, n_class, in_channels=1, seed=0, first_index=0, head="sigmoid"):
     """The phantoms as cases on disk (tests, smoke commands)."""
     os.makedirs(data_dir, exist_ok=True)
     for i, name in enumerate(names):
-        c = synthetic_case(seed, first_index + i, shape, n_class, in_channels)
+        c = synthetic_case(seed, first_index + i, shape, n_class, in_channels, head)
         np.save(os.path.join(data_dir, name + "_img.npy"), c.img)
         np.save(os.path.join(data_dir, name + "_seg.npy"), c.seg)
 
@@ -549,13 +589,14 @@ def synthetic_shape(crop):
 
 def loaders(args, rank=0, world=1):
     """{'train': CropLoader, 'eval': TileLoader, 'test': TileLoader} for --data DIR | synthetic."""
-    crop, K, C = parse_crop(args.crop), check_n_class(args.n_class), int(args.in_channels)
+    head = getattr(args, "head", "sigmoid")
+    crop, K, C = parse_crop(args.crop), check_n_class(args.n_class, head), int(args.in_channels)
     if args.data == "synthetic":
         shape = synthetic_shape(crop)
-        mk = lambda first, n: [synthetic_case(args.seed, first + i, shape, K, C) for i in range(n)]     # noqa: E731
+        mk = lambda first, n: [synthetic_case(args.seed, first + i, shape, K, C, head) for i in range(n)]     # noqa: E731
         train, val, test = mk(0, 8), mk(1000, 2), mk(2000, 2)
     elif os.path.isdir(args.data):
-        train, val, test = (open_cases(args.data, f, K, C) for f in ("train.txt", "val.txt", "test.txt"))
+        train, val, test = (open_cases(args.data, f, K, C, head=head) for f in ("train.txt", "val.txt", "test.txt"))
     else:
         raise SystemExit("--data must be 'synthetic' or a directory with <case>_img.npy / <case>_seg.npy and train.txt, val.txt, test.txt")
     steps = int(args.steps_per_epoch) or -(-len(train) // int(args.b))         # 0: one crop per training case and epoch

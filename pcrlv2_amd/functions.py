@@ -612,6 +612,37 @@ class SegHeadFn(Function):
         return out
 
 
+class SegSoftmaxHeadFn(Function):
+    """wc * CE + wd * (1 - mean_{k >= 1} Dice_k) of softmax(out_tr.final_conv(a)) against a uint8 label map -- SegHeadFn's sibling for mutually exclusive
+    classes, ONE node on pcrl_seg_mc_head_fwd / _bwd (csrc/seg_head_mc.hip).
+    -> (loss 0-d float32, sums float64 [4 K + 1] (no gradient): {I, P, G, CE} per class and the counted voxels, for logging)."""
+
+    @staticmethod
+    def forward(ctx, a, w, b, labels, wc, wd, mod):
+        dt = mod.compute_dtype
+        a = ops.to_act(a, dt)
+        loss, sums = ops.seg_mc_head_forward(a, w, b, labels, dt, wc, wd)
+        ctx.a, ctx.dt, ctx.labels, ctx.wts = a, dt, labels, (wc, wd)     # `a` is an INPUT (no reference cycle)
+        ctx.plist = (w, b)
+        ctx.pass_idx = getattr(mod, "_pass_idx", 1)
+        ctx.save_for_backward(sums)          # an OUTPUT needed in backward: never stashed on ctx directly
+        ctx.mark_non_differentiable(sums)
+        ctx.set_materialize_grads(False)
+        return loss, sums
+
+    @staticmethod
+    def backward(ctx, dloss, _dsums):
+        if dloss is None:
+            return (None,) * 7
+        w, b = ctx.plist
+        (sums,) = ctx.saved_tensors
+        dx, dw, db = ops.seg_mc_head_backward(ctx.a, w, b, ctx.labels, sums, dloss, ctx.dt, *ctx.wts, need_dx=ctx.needs_input_grad[0])
+        out = dx, _park(w, dw.view(w.shape)), _park(b, db), None, None, None, None
+        mark_final(ctx, ctx.plist)
+        ctx.a = ctx.labels = None
+        return out
+
+
 class TrilinearFn(Function):
     """F.interpolate(x, scale_factor=s, mode='trilinear')  --  models/pcrlv2_model_3d.py:125-126."""
 

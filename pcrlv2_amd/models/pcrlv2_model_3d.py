@@ -529,15 +529,28 @@ class Segmenter3d(PCRLv23d):
     (functions.UpConvsFn), then the output head and the Dice/BCE loss as one operator (functions.SegHeadFn, csrc/seg_head.hip).  The projection,
     predictor and deep-supervision heads are NOT run: their parameters have requires_grad = False here and their running statistics and counters do
     not move; `trainable_parameters()` is what the optimiser gets.  infer(x, ...) is the eval-mode forward on the inference kernels followed by
-    pcrl_seg_head_eval, infer_logits(x) the same forward followed by pcrl_seg_head_logits.  labels: uint8 [N, D, H, W], bit k = class k (classes may overlap), bit 7 = the voxel is not counted."""
+    pcrl_seg_head_eval, infer_logits(x) the same forward followed by pcrl_seg_head_logits.  labels: uint8 [N, D, H, W], bit k = class k (classes may overlap), bit 7 = the voxel is not counted.
+
+    head='softmax' (the default is 'sigmoid', everything above): n_class = K in 2..16 mutually exclusive classes, the background (class 0) counted in K;
+    labels are a LABEL MAP (bits 0..6: the class index, bit 7: not counted) and the loss is wc * cross-entropy + wd * (1 - mean Dice of the classes
+    1..K-1) on functions.SegSoftmaxHeadFn (csrc/seg_head_mc.hip).  loss, infer and infer_logits dispatch on `self.head`; infer then returns the predicted
+    label map where the sigmoid head returns the bitmask, and counts rows for all K classes.  Everything below the head is shared."""
 
     _HEADS = ("bn.", "predictor_head.", "deep_supervision_head.")
 
-    def __init__(self, n_class, in_channels=1, weights=None, act='relu', norm='bn', wb=1.0, wd=1.0):
-        if not 1 <= int(n_class) <= 7:
+    HEADS = ("sigmoid", "softmax")
+
+    def __init__(self, n_class, in_channels=1, weights=None, act='relu', norm='bn', wb=1.0, wd=1.0, head='sigmoid', wc=1.0):
+        if head not in self.HEADS:
+            raise ValueError("head must be 'sigmoid' (overlapping regions, a bitmask) or 'softmax' (mutually exclusive classes, a label map), got %r" % (head,))
+        if head == 'softmax' and not 2 <= int(n_class) <= 16:
+            raise ValueError("n_class must be in 2..16 with the softmax head (mutually exclusive classes, the background counted; a label byte holds the "
+                             "class index in bits 0..6), got %r" % (n_class,))
+        if head == 'sigmoid' and not 1 <= int(n_class) <= 7:
             raise ValueError("n_class must be in 1..7 (one bit of the label byte per class; bit 7 means 'not counted'), got %r" % (n_class,))
         super().__init__(n_class=int(n_class), act=act, norm=norm, in_channels=in_channels)
         self.n_class, self.in_channels, self.wb, self.wd = int(n_class), int(in_channels), float(wb), float(wd)
+        self.head, self.wc = head, float(wc)
         for name, p in self.named_parameters():
             if self._is_head(name):
                 p.requires_grad_(False)
@@ -611,7 +624,10 @@ class Segmenter3d(PCRLv23d):
         if not self.training:
             raise RuntimeError("Segmenter3d.loss is the TRAINING step's path; in eval mode call infer")
         fc = self.out_tr.final_conv
-        out = Fn.SegHeadFn.apply(self.features(x), fc.weight, fc.bias, labels.contiguous(), self.wb, self.wd, self.out_tr)
+        if self.head == 'softmax':      # sums: {I, P, G, CE} per class
+            out = Fn.SegSoftmaxHeadFn.apply(self.features(x), fc.weight, fc.bias, labels.contiguous(), self.wc, self.wd, self.out_tr)
+        else:
+            out = Fn.SegHeadFn.apply(self.features(x), fc.weight, fc.bias, labels.contiguous(), self.wb, self.wd, self.out_tr)
         ops.end_of_forward_join()
         return out
 
@@ -619,10 +635,14 @@ class Segmenter3d(PCRLv23d):
     def infer(self, x, labels=None, case_index=None, counts=None, want_mask=False):
         """The eval-mode forward on the inference kernels, whatever `self.training` says; nothing of the model is touched.  Prediction: z_k >= 0.
         counts int64 [cases, K, 3] (device) gets {TP, |pred|, |gt|} of sample n added at row case_index[n] (int32 [N]; None: row n of a fresh table).
-        -> (counts, loss 0-d, sums float64 [4 K + 1], predicted bitmask uint8 [N, D, H, W] | None)"""
+        -> (counts, loss 0-d, sums float64 [4 K + 1], predicted bitmask uint8 [N, D, H, W] | None)
+        Softmax head: prediction = the lowest class with the largest logit, counts rows for all K classes, and the label map in the bitmask's place."""
         self._check(x, labels)
         dt = self.compute_dtype
         fc = self.out_tr.final_conv
+        if self.head == 'softmax':
+            return ops.seg_mc_head_eval(self._infer_features(x, dt), fc.weight, fc.bias, dt, labels=None if labels is None else labels.contiguous(),
+                                        case_index=case_index, counts=counts, want_mask=want_mask, wc=self.wc, wd=self.wd)
         return ops.seg_head_eval(self._infer_features(x, dt), fc.weight, fc.bias, dt, labels=None if labels is None else labels.contiguous(),
                                  case_index=case_index, counts=counts, want_mask=want_mask, wb=self.wb, wd=self.wd)
 
@@ -638,7 +658,7 @@ class Segmenter3d(PCRLv23d):
     @torch.no_grad()
     def infer_logits(self, x, out=None, *, flip=0, accumulate=False, scale=1.0):
         """infer's forward followed by the head's logits alone (pcrl_seg_head_logits), whatever `self.training` says; nothing of the model is touched.
-        -> float32 [N, D, H, W, K] (written into `out` when given): thresholding it at 0 is infer's mask, bit for bit.  What overlap-blended
+        -> float32 [N, D, H, W, K] (written into `out` when given): thresholding it at 0 (softmax head: its lowest-index argmax) is infer's mask, bit for bit.  What overlap-blended
         sliding windows average (train_seg.sliding_window).
         With any of flip / accumulate / scale off its default the head is pcrl_seg_head_logits_acc and `out` is required: `x` is the ALREADY mirrored
         patch and `flip` (bit 0 = D, bit 1 = H, bit 2 = W) names the mirroring to undo, so each logit lands on its un-mirrored voxel of `out`;
@@ -646,6 +666,10 @@ class Segmenter3d(PCRLv23d):
         self._check(x, None)
         dt = self.compute_dtype
         fc = self.out_tr.final_conv
+        if self.head == 'softmax':      # one entry point for the plain and the accumulating store
+            if out is None and (flip != 0 or accumulate or float(scale) != 1.0):
+                raise ValueError("Segmenter3d.infer_logits: flip / accumulate / scale write into the buffer `out`, which is required with them")
+            return ops.seg_mc_head_logits(self._infer_features(x, dt), fc.weight, fc.bias, dt, out=out, flip=flip, first=not accumulate, scale=scale)
         if flip == 0 and not accumulate and float(scale) == 1.0:
             return ops.seg_head_logits(self._infer_features(x, dt), fc.weight, fc.bias, dt, out=out)
         if out is None:

@@ -1759,6 +1759,116 @@ def seg_head_logits_acc(a, w, b, dtype, out, flip=0, first=False, scale=1.0):
     return out.view(N, D, H, W, K)
 
 
+# ----------------------------------------------------------------------------------------------
+# the softmax head over mutually exclusive classes and label maps (csrc/seg_head_mc.hip): the siblings of the five wrappers above
+# ----------------------------------------------------------------------------------------------
+def _seg_mc_args(a, w, b, labels, dtype, what):
+    N, S, K, wc, bc = _seg_args(a, w, b, labels, dtype, what)
+    if not 2 <= K <= 16:
+        raise PcrlError(f"{what}: the softmax head takes 2..16 mutually exclusive classes (the background included), got a {tuple(w.shape)} weight")
+    return N, S, K, wc, bc
+
+
+def _seg_mc_ws(N, S, K, device):
+    nb = lib().call("pcrl_seg_mc_head_ws_bytes", N, S, K)
+    return workspace(nb, device), nb
+
+
+def seg_mc_head_forward(a, w, b, labels, dtype, wc=1.0, wd=1.0):
+    """wc * CE + wd * (1 - mean_{k >= 1} Dice_k) of softmax(final_conv(a)) against the uint8 label map `labels` [N,D,H,W] (bits 0..6: the class index,
+    bit 7: not counted), one operator (pcrl_seg_mc_head_fwd).
+    -> (loss 0-d float32, sums float64 [4 K + 1]: {I, P, G, CE} per class, then the counted voxels)"""
+    N, S, K, wcon, bc = _seg_mc_args(a, w, b, labels, dtype, "seg_mc_head_forward")
+    sums = torch.empty(4 * K + 1, dtype=torch.float64, device=a.device)
+    loss = _f32(1, a.device)
+    ws, nb = _seg_mc_ws(N, S, K, a.device)
+    lib().call("pcrl_seg_mc_head_fwd", a, wcon, bc, labels, sums, loss, wc, wd, ws, nb, N, S, K, dtype_code(dtype), stream_handle())
+    return loss.view(()), sums
+
+
+def seg_mc_head_backward(a, w, b, labels, sums, dloss, dtype, wc=1.0, wd=1.0, need_dx=True):
+    """Backward of seg_mc_head_forward from d loss and the forward's `sums`, both on the device (pcrl_seg_mc_head_bwd: z and p are recomputed).
+    -> (dx like `a` | None, dw float32 [K,64], db float32 [K])"""
+    N, S, K, wcon, bc = _seg_mc_args(a, w, b, labels, dtype, "seg_mc_head_backward")
+    dx = torch.empty_like(a) if need_dx else None
+    dw, db = _f32(K * 64, a.device).view(K, 64), _f32(K, a.device)
+    ws, nb = _seg_mc_ws(N, S, K, a.device)
+    lib().call("pcrl_seg_mc_head_bwd", a, wcon, bc, labels, sums, dloss.detach().reshape(1).float(), wc, wd, dx, dw, db, ws, nb, N, S, K, dtype_code(dtype),
+               stream_handle())
+    return dx, dw, db
+
+
+def seg_mc_head_eval(a, w, b, dtype, labels=None, case_index=None, counts=None, want_mask=False, wc=1.0, wd=1.0):
+    """The inference sibling (pcrl_seg_mc_head_eval): prediction = the lowest class with the largest logit; `counts` int64 [cases, K, 3] on the device gets
+    {TP, |pred|, |gt|} of sample n ADDED at row case_index[n] for ALL K classes, the background included (int32 [N] on the device; None: row n; counts
+    None: a fresh zeroed [N, K, 3]).  labels None: every voxel counted as background.
+    -> (counts, loss 0-d float32, sums float64 [4 K + 1], predicted label map uint8 [N,D,H,W] | None)"""
+    N, S, K, wcon, bc = _seg_mc_args(a, w, b, labels, dtype, "seg_mc_head_eval")
+    if counts is None:
+        counts = torch.zeros((N, K, 3), dtype=torch.int64, device=a.device)
+    _seg_counts("seg_mc_head_eval", counts, K, a.device)
+    if case_index is not None and (case_index.dtype != torch.int32 or case_index.numel() != N or not case_index.is_contiguous() or case_index.device != a.device):
+        raise PcrlError(f"seg_mc_head_eval: case_index must be a contiguous int32 [{N}] tensor on {a.device}")
+    if case_index is None and counts.shape[0] < N:
+        raise PcrlError(f"seg_mc_head_eval: counts has {counts.shape[0]} rows for {N} samples and no case_index")
+    _, D, H, W, _ = dims(a)
+    labelmap = torch.empty((N, D, H, W), dtype=torch.uint8, device=a.device) if want_mask else None
+    sums = torch.empty(4 * K + 1, dtype=torch.float64, device=a.device)
+    loss = _f32(1, a.device)
+    ws, nb = _seg_mc_ws(N, S, K, a.device)
+    lib().call("pcrl_seg_mc_head_eval", a, wcon, bc, labels, case_index, counts, counts.shape[0], labelmap, sums, loss, wc, wd, ws, nb, N, S, K,
+               dtype_code(dtype), stream_handle())
+    return counts, loss.view(()), sums, labelmap
+
+
+def seg_mc_head_logits(a, w, b, dtype, out=None, flip=0, first=True, scale=1.0):
+    """The softmax head's logits and nothing else (pcrl_seg_mc_head_logits): z float32 [N, D, H, W, K], each bit-identical to the logit seg_mc_head_eval
+    takes its maximum over.  flip / first / scale as seg_head_logits_acc: the patches were seen MIRRORED along the axes of `flip`, each logit goes to its
+    un-mirrored voxel of `out`, v = logit if first else out + logit; out = v * scale.  The defaults are the plain case (`out` is then optional)."""
+    N, S, K, wcon, bc = _seg_mc_args(a, w, b, None, dtype, "seg_mc_head_logits")
+    _, D, H, W, _ = dims(a)
+    flip = _mirror_code(flip, "seg_mc_head_logits")
+    if out is None and first:
+        out = torch.empty((N, D, H, W, K), dtype=torch.float32, device=a.device)
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.numel() != N * S * K or not out.is_contiguous() or out.device != a.device:
+        raise PcrlError(f"seg_mc_head_logits: out must be a contiguous float32 tensor of {N * S * K} elements on {a.device} (it is read unless `first`), got "
+                        f"{getattr(out, 'dtype', type(out).__name__)} {tuple(getattr(out, 'shape', ()))}")
+    scale = float(scale)
+    if not scale == scale or scale in (float("inf"), float("-inf")):
+        raise PcrlError(f"seg_mc_head_logits: scale {scale} is not finite")
+    lib().call("pcrl_seg_mc_head_logits", a, wcon, bc, out, N, S, K, dtype_code(dtype), D, H, W, flip, int(bool(first)), scale, stream_handle())
+    return out.view(N, D, H, W, K)
+
+
+def _labelmap_group(what, lab, first, n):
+    first, n = int(first), int(n)
+    if not (1 <= n <= 7 and first >= 0 and first + n <= 128):
+        raise PcrlError(f"{what}: a group is 1..7 classes inside 0..127, got first={first} n={n}")
+    if not isinstance(lab, torch.Tensor) or lab.dtype != torch.uint8 or not lab.is_cuda or not lab.is_contiguous() or lab.numel() == 0:
+        raise PcrlError(f"{what}: a non-empty contiguous uint8 label map on the GPU is expected, got {getattr(lab, 'dtype', type(lab).__name__)} on "
+                        f"{getattr(lab, 'device', '?')}")
+    return first, n
+
+
+def seg_labelmap_to_bits(lab, first, n):
+    """A label map -> the bitmask of the n <= 7 classes first .. first + n - 1 (pcrl_seg_labelmap_to_bits): bit j = (class == first + j), bit 7 carried
+    over.  What lets the bitmask tools (surface_metrics, postprocess_mask) take label maps, a group at a time."""
+    first, n = _labelmap_group("seg_labelmap_to_bits", lab, first, n)
+    out = torch.empty_like(lab)
+    lib().call("pcrl_seg_labelmap_to_bits", lab, first, n, out, lab.numel(), stream_handle())
+    return out
+
+
+def seg_labelmap_keep(lab, bits, first, n):
+    """The way back (pcrl_seg_labelmap_keep): a voxel whose class is in first .. first + n - 1 and whose bit in `bits` was cleared becomes background."""
+    first, n = _labelmap_group("seg_labelmap_keep", lab, first, n)
+    if not isinstance(bits, torch.Tensor) or bits.dtype != torch.uint8 or bits.shape != lab.shape or bits.device != lab.device or not bits.is_contiguous():
+        raise PcrlError(f"seg_labelmap_keep: bits must be a contiguous uint8 tensor like the label map {tuple(lab.shape)}")
+    out = torch.empty_like(lab)
+    lib().call("pcrl_seg_labelmap_keep", lab, bits, first, n, out, lab.numel(), stream_handle())
+    return out
+
+
 def seg_cut_patches(img, starts, crop, out=None, flip=0):
     """The crop-sized patches of one case, cut on the device (pcrl_seg_cut_patches): img [C, X, Y, Z] float32 / float16, starts int32 [n, 3] on the same
     device.  -> float32 [n, C, *crop], 0 outside the volume: data_seg.cut's image, byte for byte.  flip != 0 (a mirror code, bit 0 = x, bit 1 = y,
@@ -1785,36 +1895,30 @@ def seg_cut_patches(img, starts, crop, out=None, flip=0):
     return out
 
 
-def seg_blend(z, starts, weights, shape, labels=None, counts=None, row=0, want_mask=True, want_probs=False, want_numden=False, want_sums=True,
-              wb=1.0, wd=1.0):
-    """The per-patch logits of ONE case z float32 [P, cx, cy, cz, K] (patches in x-major order of the per-axis `starts`, three ascending int32 device
-    vectors) blended with the separable window `weights` (three float32 device vectors of the crop's sizes) into the volume `shape` = (X, Y, Z)
-    (pcrl_seg_blend): num_k = sum w z_k and den = sum w over the covering patches in ascending order, plain float32; prediction num_k >= 0.
-    labels: uint8 [X, Y, Z] on the device or None; counts: int64 [cases, K, 3], row `row` gets {TP, |pred|, |gt|} ADDED (needs want_sums).
-    -> (mask uint8 [X, Y, Z] | None, probs float32 [K, X, Y, Z] | None, sums float64 [4 K + 1] | None, loss 0-d float32 | None,
-        numden float32 [2 K + 1, X, Y, Z] | None: num per class, then den, then zbar = num / den per class)"""
+def _seg_blend(who, lo, hi, z, starts, weights, shape, labels, counts, row, want_mask, want_probs, want_numden, want_sums, wb, wd):
+    """What seg_blend and seg_mc_blend share: the checks, the outputs and the call of pcrl_<who> with lo <= K <= hi."""
     dev = z.device
     if z.dim() != 5 or z.dtype != torch.float32 or not z.is_contiguous() or not z.is_cuda:
-        raise PcrlError(f"seg_blend: z must be a contiguous float32 [P, cx, cy, cz, K] tensor on the GPU, got {z.dtype} {tuple(z.shape)} on {z.device}")
+        raise PcrlError(f"{who}: z must be a contiguous float32 [P, cx, cy, cz, K] tensor on the GPU, got {z.dtype} {tuple(z.shape)} on {z.device}")
     P, cx, cy, cz, K = z.shape
     X, Y, Z = (int(s) for s in shape)
     for name, vs, want in (("starts", starts, torch.int32), ("weights", weights, torch.float32)):
         if len(vs) != 3 or any(v.dtype != want or v.dim() != 1 or not v.is_contiguous() or v.device != dev for v in vs):
-            raise PcrlError(f"seg_blend: {name} must be three contiguous {want} vectors on {dev}")
+            raise PcrlError(f"{who}: {name} must be three contiguous {want} vectors on {dev}")
     n = [int(s.numel()) for s in starts]
     if n[0] * n[1] * n[2] != P:
-        raise PcrlError(f"seg_blend: {P} patches against start lists of {n[0]} x {n[1]} x {n[2]}")
+        raise PcrlError(f"{who}: {P} patches against start lists of {n[0]} x {n[1]} x {n[2]}")
     if [int(w.numel()) for w in weights] != [cx, cy, cz]:
-        raise PcrlError(f"seg_blend: the weight tables have {[int(w.numel()) for w in weights]} entries for a {cx} x {cy} x {cz} crop")
-    if not 1 <= K <= 7 or min(X, Y, Z) < 1:
-        raise PcrlError(f"seg_blend: 1 <= K <= 7 classes and a non-empty volume, got K = {K} and {X} x {Y} x {Z}")
+        raise PcrlError(f"{who}: the weight tables have {[int(w.numel()) for w in weights]} entries for a {cx} x {cy} x {cz} crop")
+    if not lo <= K <= hi or min(X, Y, Z) < 1:
+        raise PcrlError(f"{who}: {lo} <= K <= {hi} classes and a non-empty volume, got K = {K} and {X} x {Y} x {Z}")
     V = X * Y * Z
-    _seg_labels("seg_blend", labels, V, dev)
+    _seg_labels(who, labels, V, dev)
     crow = None
     if counts is not None:
-        _seg_counts("seg_blend", counts, K, dev)
+        _seg_counts(who, counts, K, dev)
         if not 0 <= int(row) < counts.shape[0] or not want_sums:
-            raise PcrlError(f"seg_blend: row {row} of a counts table with {counts.shape[0]} rows (counts come with the sums)")
+            raise PcrlError(f"{who}: row {row} of a counts table with {counts.shape[0]} rows (counts come with the sums)")
         crow = counts[int(row)]
     mask = torch.empty((X, Y, Z), dtype=torch.uint8, device=dev) if want_mask else None
     probs = torch.empty((K, X, Y, Z), dtype=torch.float32, device=dev) if want_probs else None
@@ -1823,11 +1927,31 @@ def seg_blend(z, starts, weights, shape, labels=None, counts=None, row=0, want_m
     nb = 0
     if want_sums:
         sums, loss = torch.empty(4 * K + 1, dtype=torch.float64, device=dev), _f32(1, dev)
-        nb = lib().call("pcrl_seg_blend_ws_bytes", X, Y, Z)
+        nb = lib().call(f"pcrl_{who}_ws_bytes", X, Y, Z)
         ws = workspace(nb, dev)
-    lib().call("pcrl_seg_blend", z, P, *starts, *n, *weights, cx, cy, cz, X, Y, Z, K, labels, mask, probs, numden, crow, sums, loss, wb, wd, ws, nb,
+    lib().call(f"pcrl_{who}", z, P, *starts, *n, *weights, cx, cy, cz, X, Y, Z, K, labels, mask, probs, numden, crow, sums, loss, wb, wd, ws, nb,
                stream_handle())
     return mask, probs, sums, None if loss is None else loss.view(()), numden
+
+
+
+def seg_blend(z, starts, weights, shape, labels=None, counts=None, row=0, want_mask=True, want_probs=False, want_numden=False, want_sums=True,
+              wb=1.0, wd=1.0):
+    """The per-patch logits of ONE case z float32 [P, cx, cy, cz, K] (patches in x-major order of the per-axis `starts`, three ascending int32 device
+    vectors) blended with the separable window `weights` (three float32 device vectors of the crop's sizes) into the volume `shape` = (X, Y, Z)
+    (pcrl_seg_blend): num_k = sum w z_k and den = sum w over the covering patches in ascending order, plain float32; prediction num_k >= 0.
+    labels: uint8 [X, Y, Z] on the device or None; counts: int64 [cases, K, 3], row `row` gets {TP, |pred|, |gt|} ADDED (needs want_sums).
+    -> (mask uint8 [X, Y, Z] | None, probs float32 [K, X, Y, Z] | None, sums float64 [4 K + 1] | None, loss 0-d float32 | None,
+        numden float32 [2 K + 1, X, Y, Z] | None: num per class, then den, then zbar = num / den per class)"""
+    return _seg_blend("seg_blend", 1, 7, z, starts, weights, shape, labels, counts, row, want_mask, want_probs, want_numden, want_sums, wb, wd)
+
+
+def seg_mc_blend(z, starts, weights, shape, labels=None, counts=None, row=0, want_mask=True, want_probs=False, want_numden=False, want_sums=True,
+                 wc=1.0, wd=1.0):
+    """seg_blend's sibling for the softmax head (pcrl_seg_mc_blend; 2 <= K <= 16): the same accumulation; the prediction is the LOWEST class with the
+    largest num_k, probs the softmax of zbar = num / den, labels a label map, sums / loss the softmax head's, counts rows for all K classes.
+    -> (label map uint8 [X, Y, Z] | None, probs float32 [K, X, Y, Z] | None, sums float64 [4 K + 1] | None, loss 0-d float32 | None, numden | None)"""
+    return _seg_blend("seg_mc_blend", 2, 16, z, starts, weights, shape, labels, counts, row, want_mask, want_probs, want_numden, want_sums, wc, wd)
 
 
 # ----------------------------------------------------------------------------------------------

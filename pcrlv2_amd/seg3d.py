@@ -30,6 +30,14 @@ logits of all passes are averaged in the sliding window's one per-case buffer be
 
 `prepare` writes DIR from raw NIfTI-1 / .npy volumes (crop to the non-zero box, per-case normalisation, resampling to a common spacing, label values
 to the bitmask) and `restore` takes stored predictions back to the original grid (pcrlv2_amd/seg_prep.py, csrc/seg_prep.hip).
+
+`train --head softmax [--wc W]`: `--n_class K` in 2..16 MUTUALLY EXCLUSIVE classes with the background as class 0; <case>_seg.npy
+is then a label map (bits 0..6: the class index, bit 7: not counted) and the loss is wc * cross-entropy + wd * (1 - mean Dice of the classes 1..K-1)
+(csrc/seg_head_mc.hip).  `--head sigmoid` (bitmasks, the default) is everything above.  `predict` takes the head kind from the checkpoint and writes
+label maps for a softmax one (and leaves head.txt next to them), blended, mirrored and ensembled through the label-map blend (pcrl_seg_mc_blend).
+`prepare --classes "1;2;3,4"` writes label maps (set i -> class i + 1, everything else background; not with --regions); `restore --labelmap --paint
+v0,v1,..` paints class INDEX i with v_i; `score --labelmap` and `postprocess --labelmap` take label maps (--n_class K counts the background), the classes
+1..K-1 in groups of at most 7 through the bitmask kernels; without --labelmap both refuse a directory whose head.txt says softmax.
 """
 from __future__ import annotations
 
@@ -40,8 +48,11 @@ import sys
 def check_train(args):
     """Every refused combination exits with its message, before anything touches a GPU."""
     from .data_seg import check_n_class, parse_crop
-    check_n_class(args.n_class)
+    head, wc = getattr(args, "head", "sigmoid"), float(getattr(args, "wc", 1.0))      # a namespace from before the options existed is a sigmoid one
+    check_n_class(args.n_class, head)
     parse_crop(args.crop)
+    if not wc >= 0:
+        raise SystemExit(f"--wc {wc}: the weight of the cross-entropy term of --head softmax is a non-negative number")
     if args.in_channels < 1:
         raise SystemExit(f"--in_channels {args.in_channels}: at least 1")
     if args.phase == "finetune" and not args.weights:
@@ -126,6 +137,9 @@ def build_parser():
     tr.add_argument("--phase", default="finetune", choices=("finetune", "scratch"))
     tr.add_argument("--weights", default="", help="3D pre-training checkpoint (--phase finetune)")
     tr.add_argument("--n_class", type=int, default=3, help="classes = bits of the label byte, 1..7")
+    tr.add_argument("--head", default="sigmoid", help="sigmoid: overlapping regions, labels are bitmasks, Dice/BCE (the default) | softmax: 2..16 mutually "
+                    "exclusive classes with the background as class 0, labels are label maps, Dice/cross-entropy")
+    tr.add_argument("--wc", type=float, default=1.0, help="--head softmax: the weight of the cross-entropy term")
     tr.add_argument("--in_channels", type=int, default=1)
     tr.add_argument("--crop", default="64,64,32", help="training crop = evaluation patch, x,y,z, multiples of 8")
     tr.add_argument("--b", type=int, default=8, help="batch size PER PROCESS")
@@ -180,6 +194,8 @@ def build_parser():
     pp.add_argument("--list", required=True, help="file of case names (in --pred, or a path)")
     pp.add_argument("--out", required=True, help="output directory for the cleaned <case>_pred.npy; not --pred")
     pp.add_argument("--n_class", type=int, default=3, help="classes = bits of the mask byte, 1..7")
+    pp.add_argument("--labelmap", action="store_true", help="the predictions are label maps (--head softmax); --n_class K counts the background, 2..16; "
+                    "the background is never touched")
     _cleanup_options(pp)
     pp.add_argument("--gpu", type=int, default=0)
     sc = sub.add_parser("score", help="Dice, HD95, HD and ASSD of stored <case>_pred.npy against <case>_seg.npy")
@@ -187,6 +203,8 @@ def build_parser():
     sc.add_argument("--list", required=True, help="file of case names (in --data, or a path)")
     sc.add_argument("--pred", required=True, help="directory with <case>_pred.npy (the --out of `predict`)")
     sc.add_argument("--n_class", type=int, default=3, help="classes = bits of the label byte, 1..7")
+    sc.add_argument("--labelmap", action="store_true", help="ground truth and predictions are label maps (--head softmax); --n_class K counts the "
+                    "background, 2..16; one row per (case, class 1..K-1)")
     sc.add_argument("--spacing", default="1,1,1", help="voxel size sx,sy,sz; a case's <case>_spacing.npy replaces it")
     sc.add_argument("--csv", default="", help="also write case,class,dice,hd95,hd,assd,n_pred,n_gt to this file")
     sc.add_argument("--gpu", type=int, default=0)
@@ -194,7 +212,9 @@ def build_parser():
     pe.add_argument("--data", required=True, help="directory the manifest's paths are relative to")
     pe.add_argument("--manifest", required=True, help="one case per line: name seg_path|- img_path [img_path ...]")
     pe.add_argument("--save", required=True, help="output directory (the --data of train / predict / score)")
-    pe.add_argument("--regions", required=True, help="K = 1..7 sets of label values, bit k = set k: \"1,2,4;1,4;4\"")
+    pe.add_argument("--regions", default=None, help="K = 1..7 sets of label values, bit k = set k: \"1,2,4;1,4;4\" (this or --classes)")
+    pe.add_argument("--classes", default=None, help="1..15 DISJOINT sets of label values, set i = class index i + 1 of a label map (--head softmax), a value "
+                    "in no set = background 0: \"1;2;3,4\"")
     pe.add_argument("--spacing", default="keep", help="target voxel size sx,sy,sz, or `keep`")
     pe.add_argument("--crop_nonzero", type=int, default=1, help="1: crop to the bounding box of the non-zero voxels and normalise over them; 0: neither")
     pe.add_argument("--norm", default="zscore", help="zscore | percentile | window | none")
@@ -213,6 +233,8 @@ def build_parser():
     rs.add_argument("--list", required=True, help="file of case names (in --prep, or a path)")
     rs.add_argument("--out", required=True, help="output directory; not --pred")
     rs.add_argument("--paint", default=None, help="also write <case>_label.npy: class k painted with the k-th value, later over earlier: \"2,1,4\"")
+    rs.add_argument("--labelmap", action="store_true", help="the predictions are label maps (--head softmax): --paint v0,v1,.. gives the value of class "
+                    "INDEX i, the background first")
     rs.add_argument("--nifti", action="store_true", help="also write .nii.gz with the stored header's geometry")
     rs.add_argument("--gpu", type=int, default=0)
     return ap

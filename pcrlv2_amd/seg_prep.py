@@ -32,6 +32,10 @@ prep_spacing, stats [C][4] = mean, std, lo, hi as used, norm, crop_nonzero, head
 `restore` takes `<case>_pred.npy` on the prepared grid back to the original one: nearest neighbour through the inverse tables inside the box, 0
 outside; `--paint v0,v1,...` also writes `<case>_label.npy`, class k painted with v_k in order, later over earlier; `--nifti` writes `.nii.gz` with
 the stored header's geometry.  DESIGN.md section 20.
+
+Label maps: `prepare --classes "1;2;3,4"` instead of --regions writes <case>_seg.npy as a label map for --head softmax (set i ->
+class index i + 1, a value in no set -> 0; a value in two sets is refused), `restore --labelmap --paint v0,v1,..` paints class INDEX i with v_i.  Both
+are second builders of the kernels' 256-entry tables (class_table, labelmap_paint_table); the kernels are unchanged.
 """
 from __future__ import annotations
 
@@ -91,6 +95,58 @@ def region_table(regions):
     return tab
 
 
+MAX_CLASSES = 16      # label maps (--classes, --labelmap): the classes of the softmax head, the background included
+
+
+def parse_classes(text):
+    """--classes '1;2;3,4' -> [frozenset, ...]: 1..15 non-empty, DISJOINT sets of label values 0..255; set i becomes class index i + 1 of a label map,
+    a value in no set the background 0."""
+    sets = []
+    for part in str(text).split(";"):
+        try:
+            vals = [int(t) for t in part.split(",")]
+        except ValueError:
+            raise SystemExit(f"--classes {text}: `{part}` is not a comma-separated list of integers") from None
+        if not vals or any(v < 0 or v > 255 for v in vals):
+            raise SystemExit(f"--classes {text}: every set holds label values 0..255")
+        for i, s in enumerate(sets):
+            both = sorted(s & set(vals))
+            if both:
+                raise SystemExit(f"--classes {text}: label value {both[0]} is in set {i + 1} and in set {len(sets) + 1}; the classes of a label map are "
+                                 "mutually exclusive (overlapping regions are --regions, with the sigmoid head)")
+        sets.append(frozenset(vals))
+    if not 1 <= len(sets) <= MAX_CLASSES - 1:
+        raise SystemExit(f"--classes {text}: 1..{MAX_CLASSES - 1} semicolon-separated sets (set i = class i + 1 of the label map; 0 is the background)")
+    return sets
+
+
+def class_table(classes):
+    """uint8 [256], the second builder of pcrl_segprep_resample's table: entry v is i + 1 where v is in set i, else 0 (the background)."""
+    tab = np.zeros(256, dtype=np.uint8)
+    for i, s in enumerate(classes):
+        for v in s:
+            tab[v] = np.uint8(i + 1)
+    return tab
+
+
+def parse_labelmap_paint(text):
+    """--labelmap --paint 'v0,v1,..': the label value of class INDEX i, 2..16 values 0..255 (v0 paints the background)."""
+    try:
+        vals = [int(t) for t in str(text).split(",")]
+    except ValueError:
+        vals = []
+    if not 2 <= len(vals) <= MAX_CLASSES or any(v < 0 or v > 255 for v in vals):
+        raise SystemExit(f"--paint {text}: with --labelmap 2..{MAX_CLASSES} comma-separated label values 0..255, one per class index, the background first")
+    return vals
+
+
+def labelmap_paint_table(values):
+    """uint8 [256], the second builder of pcrl_segprep_restore's paint table: entry i is v_i for a class index i < K, everything else 0."""
+    tab = np.zeros(256, dtype=np.uint8)
+    tab[:len(values)] = np.asarray(values, dtype=np.uint8)
+    return tab
+
+
 def parse_paint(text):
     """'2,1,4' -> [2, 1, 4]: the label value of class k, 1..7 values 0..255."""
     try:
@@ -140,6 +196,7 @@ class PrepConfig:
     mean: float = 0.0
     std: float = 1.0
     float16: bool = False
+    classes: list | None = None           # --classes: the label values become a LABEL MAP (class_table) and `regions` is empty
 
 
 def parse_manifest(path, data_dir):
@@ -178,13 +235,18 @@ def parse_manifest(path, data_dir):
 
 def check_prepare(args):
     """Every refused combination exits with its message, before anything touches a GPU.  -> (PrepConfig, manifest, split or None)"""
-    regions = parse_regions(args.regions)
+    classes_arg = getattr(args, "classes", None)
+    if (args.regions is None) == (classes_arg is None):
+        raise SystemExit("prepare: exactly one of --regions \"1,2,4;1,4;4\" (overlapping regions -> a bitmask, the sigmoid head) and --classes \"1;2;3,4\" "
+                         "(mutually exclusive classes -> a label map, --head softmax)")
+    classes = parse_classes(classes_arg) if classes_arg is not None else None
+    regions = parse_regions(args.regions) if classes is None else []
     spacing = parse_spacing(args.spacing)
     if args.crop_nonzero not in (0, 1):
         raise SystemExit(f"--crop_nonzero {args.crop_nonzero}: 1 or 0")
     if args.norm not in NORMS:
         raise SystemExit(f"--norm {args.norm}: one of {', '.join(NORMS)}")
-    cfg = PrepConfig(regions=regions, spacing=spacing, crop_nonzero=bool(args.crop_nonzero), norm=args.norm, float16=bool(args.float16))
+    cfg = PrepConfig(regions=regions, spacing=spacing, crop_nonzero=bool(args.crop_nonzero), norm=args.norm, float16=bool(args.float16), classes=classes)
     if args.percentiles is not None and args.norm != "percentile":
         raise SystemExit("--percentiles belongs to --norm percentile")
     if args.norm == "percentile":
@@ -220,7 +282,10 @@ def check_prepare(args):
 def check_restore(args):
     """-> (paint values or None, [(name, pred path, prep path)]); every refusal before anything touches a GPU."""
     from .data_seg import read_list
-    paint = parse_paint(args.paint) if args.paint is not None else None
+    if getattr(args, "labelmap", False):
+        paint = parse_labelmap_paint(args.paint) if args.paint is not None else None
+    else:
+        paint = parse_paint(args.paint) if args.paint is not None else None
     if os.path.abspath(args.out) == os.path.abspath(args.pred):
         raise SystemExit("--out must not be --pred (both hold <case>_pred.npy)")
     plan = []
@@ -451,7 +516,9 @@ def prepare_case(channels, seg, spacing, cfg, device, name="case", timing=None):
     if OV >= 2 ** 31:
         raise PrepError(f"{name}: the prepared grid {out_shape} has 2^31 voxels or more")
     tab_i, tab_w = resample_tables(box[3:], out_shape)
-    tabs = np.concatenate([tab_w.view(np.uint8), tab_i.view(np.uint8), region_table(cfg.regions)])
+    # the kernel maps label bytes through ONE 256-entry table; K reaches it only to be checked, so a label-map table travels as one "region"
+    table, k_dev = (class_table(cfg.classes), 1) if cfg.classes else (region_table(cfg.regions), len(cfg.regions))
+    tabs = np.concatenate([tab_w.view(np.uint8), tab_i.view(np.uint8), table])
     tabs_d = torch.from_numpy(tabs).to(device)
     tw_d = tabs_d[:tab_w.nbytes].view(torch.float64)
     ti_d = tabs_d[tab_w.nbytes:tab_w.nbytes + tab_i.nbytes].view(torch.int32)
@@ -460,7 +527,7 @@ def prepare_case(channels, seg, spacing, cfg, device, name="case", timing=None):
     out_d = torch.empty(C * OV * oes + OV, dtype=torch.uint8, device=device)
     img_d = out_d[:C * OV * oes].view(odt).view(C, *out_shape)
     lab_d = out_d[C * OV * oes:].view(*out_shape)
-    gpu_resample(src, lab, box, out_shape, ti_d, tw_d, stats_d, clip_d, reg_d, len(cfg.regions), use_mask, img_d, lab_d)
+    gpu_resample(src, lab, box, out_shape, ti_d, tw_d, stats_d, clip_d, reg_d, k_dev, use_mask, img_d, lab_d)
     t0 = _tick(timing, "resample", t0, device)
     out = out_d.cpu().numpy()                                                          # the one download
     if stats_d is not None and cfg.norm != "window":
@@ -475,7 +542,7 @@ def prepare_case(channels, seg, spacing, cfg, device, name="case", timing=None):
     return {"img": img, "seg": out[C * OV * oes:].reshape(out_shape), "spacing": prep_spacing, "meta": meta}
 
 
-def restore_case(pred, meta, device, paint=None):
+def restore_case(pred, meta, device, paint=None, labelmap=False):
     """pred uint8 [X', Y', Z'] on the prepared grid, meta as prepare_case wrote it -> (mask uint8 [X, Y, Z] on the original grid, label map or None)."""
     prep_shape = tuple(int(v) for v in meta["prep_shape"])
     pred = np.ascontiguousarray(pred)
@@ -485,7 +552,8 @@ def restore_case(pred, meta, device, paint=None):
     box = (b[0], b[2], b[4], b[1] - b[0], b[3] - b[2], b[5] - b[4])
     orig = tuple(int(v) for v in meta["orig_shape"])
     tab = restore_tables(box[3:], prep_shape)
-    parts = [tab.view(np.uint8)] + ([paint_table(paint)] if paint is not None else []) + [pred.reshape(-1)]
+    painter = labelmap_paint_table if labelmap else paint_table
+    parts = [tab.view(np.uint8)] + ([painter(paint)] if paint is not None else []) + [pred.reshape(-1)]
     up = torch.from_numpy(np.concatenate(parts)).to(device)                            # one upload
     tab_d = up[:tab.nbytes].view(torch.int32)
     off = tab.nbytes + (256 if paint is not None else 0)
@@ -613,7 +681,7 @@ def run_restore(args, log=print):
     for name, pred_path, prep_path in plan:
         with np.load(prep_path) as z:
             meta = {k: z[k] for k in z.files}
-        mask, label = restore_case(np.load(pred_path), meta, device, paint)
+        mask, label = restore_case(np.load(pred_path), meta, device, paint, labelmap=bool(getattr(args, "labelmap", False)))
         np.save(os.path.join(args.out, name + "_pred.npy"), mask)
         if label is not None:
             np.save(os.path.join(args.out, name + "_label.npy"), label)

@@ -25,6 +25,12 @@ prediction and the sliding window never see it.
 `predict --mirror` / `--weights a.pt,b.pt` and `train --val_mirror` (sliding_window(mirror=, models=)): every patch batch is also
 shown mirrored and to every checkpoint, and the un-mirrored logits of all passes are averaged in the sliding window's one per-case buffer
 (csrc/seg_head.hip's accumulating logits kernel, csrc/seg_blend.hip's mirrored cutter).  At `none` and one checkpoint nothing changes.
+
+Head kinds: a Segmenter3d(head='softmax') trains and evaluates on label maps through the same loop -- `_held_out` takes the
+mean per-case Dice over the classes 1..K-1 (dice_from_counts(first=1); the background is excluded) and the softmax form of loss_from_sums.  The kind is
+saved as val['head'] in a _best.pt (softmax only) and is in the `opt` of a last-epoch checkpoint; load_segmenter reads it (checkpoint_head: a checkpoint
+without it is a sigmoid one) and check_ensemble refuses mixed kinds.  sliding_window blends a softmax model's logits with ops.seg_mc_blend; `predict` of one leaves head.txt next to its label maps, and
+`score` / `postprocess` take them with --labelmap (the classes 1..K-1 in groups of at most 7 through the bitmask machinery) and refuse them without.
 """
 from __future__ import print_function
 
@@ -44,27 +50,53 @@ from .optim import FusedSGD
 from .seg_prep import lerp
 
 
-def dice_from_counts(counts):
-    """Host, float64: counts [cases][K][3] = {TP, |pred|, |gt|} (nested lists or a tensor) -> (per-class Dice averaged over the cases [K], their mean over
-    the classes).  A (case, class) pair with empty prediction AND empty ground truth scores 1; an empty prediction against a non-empty ground truth
-    scores 0 by the formula.  No cases: NaN."""
+def dice_from_counts(counts, first=0):
+    """Host, float64: counts [cases][K][3] = {TP, |pred|, |gt|} (nested lists or a tensor) -> (per-class Dice averaged over the cases [K - first], their
+    mean over the classes).  A (case, class) pair with empty prediction AND empty ground truth scores 1; an empty prediction against a non-empty ground
+    truth scores 0 by the formula.  No cases: NaN.  `first`: the first class that enters -- 1 for the softmax head, whose class 0 is the background."""
     rows = counts.tolist() if torch.is_tensor(counts) else counts
     if not rows:
         return [], float("nan")
     K = len(rows[0])
     per = []
-    for k in range(K):
+    for k in range(first, K):
         ds = [1.0 if (r[k][1] + r[k][2]) == 0 else 2.0 * float(r[k][0]) / float(r[k][1] + r[k][2]) for r in rows]
         per.append(sum(ds) / len(ds))
-    return per, sum(per) / K
+    return per, sum(per) / (K - first)
 
 
-def loss_from_sums(sums, K, wb=1.0, wd=1.0):
-    """Host: the operator's loss from its float64 sums [4 K + 1] ({I, P, G, BCE} per class, then the counted voxels), here over a whole pass."""
+def loss_from_sums(sums, K, wb=1.0, wd=1.0, head="sigmoid", wc=1.0):
+    """Host: the operator's loss from its float64 sums [4 K + 1] ({I, P, G, BCE} per class, then the counted voxels), here over a whole pass.
+    head='softmax': {I, P, G, CE} per class; wc * sum CE / Mc + wd * (1 - mean Dice of the classes 1..K-1)."""
     mc = sums[4 * K]
+    if head == "softmax":
+        ce = sum(sums[4 * k + 3] for k in range(K)) / mc if mc > 0 else 0.0
+        dice = sum((2.0 * sums[4 * k] + 1.0) / (sums[4 * k + 1] + sums[4 * k + 2] + 1.0) for k in range(1, K)) / (K - 1)
+        return wc * ce + wd * (1.0 - dice)
     bce = sum(sums[4 * k + 3] for k in range(K)) / (mc * K) if mc > 0 else 0.0
     dice = sum((2.0 * sums[4 * k] + 1.0) / (sums[4 * k + 1] + sums[4 * k + 2] + 1.0) for k in range(K)) / K
     return wb * bce + wd * (1.0 - dice)
+
+
+HEAD_FILE = "head.txt"      # next to the <case>_pred.npy of a softmax model: what tells `score` / `postprocess` that the bytes are class indices
+
+
+def write_head_kind(out_dir, head):
+    """`predict` (and `postprocess --labelmap`) of a softmax model leave DIR/head.txt = 'softmax'; a sigmoid run writes nothing and removes a stale one."""
+    path = os.path.join(out_dir, HEAD_FILE)
+    if head == "softmax":
+        with open(path, "w") as f:
+            f.write("softmax\n")
+    elif os.path.exists(path):
+        os.remove(path)
+
+
+def refuse_labelmap_prediction(pred_dir, command):
+    """A directory of label maps read as bitmasks would be scored or cleaned wrongly without any error: class index 3 is 'regions 0 and 1'."""
+    path = os.path.join(pred_dir, HEAD_FILE)
+    if os.path.exists(path) and open(path).read().strip() == "softmax":
+        raise SystemExit(f"{command}: {pred_dir} holds the label maps of a --head softmax model ({HEAD_FILE} says so): pass --labelmap and --n_class K with "
+                         "the background counted")
 
 
 def higher_dice(val, best):
@@ -124,8 +156,14 @@ def _held_out(model, n_cases, steps, group, step_sums):
 
     host = _loop.held_out_pass(steps, group, acc, per_step, also_read=counts_into_acc)
     table = [[[int(v) for v in host[ns + (c * K + k) * 3:ns + (c * K + k) * 3 + 3]] for k in range(K)] for c in range(n_cases)]
-    per, mean = dice_from_counts(table)
-    return {"loss": loss_from_sums(host[:ns], K, model.wb, model.wd) if n_cases else float("nan"), "dice": per, "mean_dice": mean, "cases": n_cases}
+    head = getattr(model, "head", "sigmoid")
+    per, mean = dice_from_counts(table, first=int(head == "softmax"))
+    val = {"loss": loss_from_sums(host[:ns], K, model.wb, model.wd, head, getattr(model, "wc", 1.0)) if n_cases else float("nan"), "dice": per,
+           "mean_dice": mean, "cases": n_cases}
+    if head != "sigmoid":        # what load_segmenter reads from a _best.pt.  Deliberately NOT written for the sigmoid head: its _best.pt stays
+        # byte for byte what it was, and a checkpoint without the entry is a sigmoid one (checkpoint_head)
+        val["head"] = head
+    return val
 
 
 def evaluate(model, loader, group=None):
@@ -164,6 +202,8 @@ def sliding_window(model, case, crop, b, overlap, window, *, counts=None, row=0,
     codes = sorted({int(c) for c in mirror})
     if not nets or not codes or codes[0] < 0 or codes[-1] > 7:
         raise ValueError(f"sliding_window: mirror codes are integers 0..7 and `models` is not empty, got mirror {tuple(mirror)} and {len(nets)} models")
+    if any(getattr(net, "head", "sigmoid") != getattr(model, "head", "sigmoid") for net in nets):
+        raise ValueError("sliding_window: every model of `models` must have the head kind of `model`")
     if models is not None and any(int(net.n_class) != K for net in nets):
         raise ValueError(f"sliding_window: every model of `models` must have the {K} classes of `model`, got {[int(net.n_class) for net in nets]}")
     passes = [(net, code) for net in nets for code in codes]
@@ -185,9 +225,14 @@ def sliding_window(model, case, crop, b, overlap, window, *, counts=None, row=0,
             last = i == len(passes) - 1
             net.infer_logits(_ops.seg_cut_patches(img, st[a:a + b], crop, flip=code), out=z[a:a + b], flip=code, accumulate=i > 0,
                              scale=np.float32(1.0 / len(passes)) if last else 1.0)
-    mask, probs, sums, _, _ = _ops.seg_blend(z, [torch.tensor(a, dtype=torch.int32, device=dev) for a in axes], [torch.from_numpy(w).to(dev) for w in weights],
-                                             case.shape, labels=labels, counts=counts, row=row, want_mask=want_mask, want_probs=want_probs,
-                                             want_sums=labels is not None or counts is not None, wb=model.wb, wd=model.wd)
+    sd, wdev = [torch.tensor(a, dtype=torch.int32, device=dev) for a in axes], [torch.from_numpy(w).to(dev) for w in weights]
+    want_sums = labels is not None or counts is not None
+    if getattr(model, "head", "sigmoid") == "softmax":       # only the logits call (inside infer_logits) and the blend call differ between the heads
+        mask, probs, sums, _, _ = _ops.seg_mc_blend(z, sd, wdev, case.shape, labels=labels, counts=counts, row=row, want_mask=want_mask,
+                                                    want_probs=want_probs, want_sums=want_sums, wc=model.wc, wd=model.wd)
+    else:
+        mask, probs, sums, _, _ = _ops.seg_blend(z, sd, wdev, case.shape, labels=labels, counts=counts, row=row, want_mask=want_mask, want_probs=want_probs,
+                                                 want_sums=want_sums, wb=model.wb, wd=model.wd)
     return mask, probs, sums
 
 
@@ -242,7 +287,8 @@ def _train_segmenter(args, distributed):
         held_out, tail = evaluate, ""
 
     def make(rank):
-        return Segmenter3d(args.n_class, in_channels=args.in_channels, weights=args.weights if args.phase == "finetune" else None)
+        return Segmenter3d(args.n_class, in_channels=args.in_channels, weights=args.weights if args.phase == "finetune" else None,
+                           head=getattr(args, "head", "sigmoid"), wc=float(getattr(args, "wc", 1.0)))
 
     task = _loop.Task(
         make_model=make,
@@ -293,9 +339,26 @@ def state_dict_sizes(sd):
     return int(sd["out_tr.final_conv.weight"].shape[0]), int(sd["down_tr64.ops.0.conv1.weight"].shape[1])
 
 
-def check_ensemble(files, state_dicts):
-    """The checkpoints of an ensemble agree in n_class and in_channels, or the first one that differs from the first exits with a message naming both
-    files.  On the host, on the state dicts.  -> (n_class, in_channels)"""
+def checkpoint_head(ckpt):
+    """The head kind of a checkpoint of `seg3d.py train`: the validation dictionary of a _best.pt (val['head']) or the options of a last-epoch one
+    (opt.head); a checkpoint with neither is a sigmoid one."""
+    val, opt = ckpt.get("val"), ckpt.get("opt")
+    head = val.get("head") if isinstance(val, dict) and "head" in val else getattr(opt, "head", "sigmoid")
+    return _data.check_head(head)
+
+
+def read_head(weights):
+    return checkpoint_head(torch.load(weights, map_location="cpu", weights_only=False))
+
+
+def check_ensemble(files, state_dicts, heads=None):
+    """The checkpoints of an ensemble agree in n_class and in_channels (and, with `heads`, in the head kind), or the first one that differs from the
+    first exits with a message naming both files.  On the host, on the state dicts.  -> (n_class, in_channels)"""
+    if heads is not None:
+        for f, h in zip(files[1:], heads[1:]):
+            if h != heads[0]:
+                raise SystemExit(f"--weights: {f} was trained with --head {h}, {files[0]} with --head {heads[0]}: the checkpoints of an ensemble must "
+                                 "have the same head kind (a bitmask and a label map cannot be averaged)")
     first = state_dict_sizes(state_dicts[0])
     for f, sd in zip(files[1:], state_dicts[1:]):
         got = state_dict_sizes(sd)
@@ -305,10 +368,10 @@ def check_ensemble(files, state_dicts):
     return first
 
 
-def load_segmenter(weights, device, amp=False, state_dict=None):
+def load_segmenter(weights, device, amp=False, state_dict=None, head=None):
     sd = read_state_dict(weights) if state_dict is None else state_dict
     n_class, in_channels = state_dict_sizes(sd)
-    model = Segmenter3d(n_class, in_channels=in_channels)
+    model = Segmenter3d(n_class, in_channels=in_channels, head=read_head(weights) if head is None else head)
     model.load_state_dict(sd)
     model = model.to(device)
     if amp:
@@ -317,7 +380,7 @@ def load_segmenter(weights, device, amp=False, state_dict=None):
 
 
 def predict_case(model, case, crop, b):
-    """The predicted bitmask uint8 [X, Y, Z] of one case, stitched from its tiles (each voxel from the one tile that counts it)."""
+    """The predicted bitmask (softmax head: label map) uint8 [X, Y, Z] of one case, stitched from its tiles (each voxel from the one tile that counts it)."""
     dev = next(model.parameters()).device
     out = np.zeros(case.shape, dtype=np.uint8)
     for x, lab, _, starts in _data.TileLoader([case], crop, b):
@@ -336,33 +399,36 @@ def predict(args, log=print):
     mirror = _data.parse_mirror(getattr(args, "mirror", None))
     files = split_weights(args.weights)
     state_dicts = [read_state_dict(f) for f in files]
-    check_ensemble(files, state_dicts)       # on the host, before any model goes to the device
+    heads = [read_head(f) for f in files]
+    check_ensemble(files, state_dicts, heads)       # on the host, before any model goes to the device
     # mirrored passes and ensembles add logits into sliding_window's buffer: they take that path also at --overlap 0, where every voxel has one patch
     # and the mask does not depend on the (positive) window
     sliding = overlap > 0 or len(mirror) > 1 or len(files) > 1
     device = torch.device("cuda", args.gpu)
     torch.cuda.set_device(device)
-    models = [load_segmenter(f, device, args.amp, state_dict=sd) for f, sd in zip(files, state_dicts)]
+    models = [load_segmenter(f, device, args.amp, state_dict=sd, head=h) for f, sd, h in zip(files, state_dicts, heads)]
     model = models[0]
     del state_dicts
     if rules is not None:
         rules = (resolve_keep(rules[0], model.n_class),) + rules[1:]
     os.makedirs(args.out, exist_ok=True)
+    write_head_kind(args.out, model.head)
+    clean = postprocess_labelmap if model.head == "softmax" else postprocess_mask
     names = _data.read_list(args.data, args.list)
     for name in names:
-        case = _data.open_case(args.data, name, model.n_class, model.in_channels, need_seg=False)
+        case = _data.open_case(args.data, name, model.n_class, model.in_channels, need_seg=False, head=model.head)
         case.seg = None          # the prediction does not look at labels
         if sliding:
             mask, probs, _ = sliding_window(model, case, crop, args.b, overlap, window, want_probs=want_probs, mirror=mirror, models=models)
             if rules is not None:
-                mask = postprocess_mask(mask, model.n_class, *rules)[0]
+                mask = clean(mask, model.n_class, *rules)[0]
             np.save(os.path.join(args.out, name + "_pred.npy"), mask.cpu().numpy())
             if want_probs:
                 np.save(os.path.join(args.out, name + "_prob.npy"), probs.half().cpu().numpy())
         else:
             mask = predict_case(model, case, crop, args.b)
             if rules is not None:         # the stitched mask is on the host: one upload
-                mask = postprocess_mask(torch.from_numpy(mask).to(device), model.n_class, *rules)[0].cpu().numpy()
+                mask = clean(torch.from_numpy(mask).to(device), model.n_class, *rules)[0].cpu().numpy()
             np.save(os.path.join(args.out, name + "_pred.npy"), mask)
     log(f"[seg3d] {len(names)} masks written to {args.out}")
     return len(names)
@@ -401,6 +467,33 @@ def postprocess_mask(mask, K, keep_largest=(), min_voxels=0, connectivity=6):
     return mask, report
 
 
+def postprocess_labelmap(lab, K, keep_largest=(), min_voxels=0, connectivity=6):
+    """postprocess_mask for a device uint8 [X, Y, Z] LABEL MAP of K classes (0 = background, which no rule touches): the classes 1..K-1 go through the
+    bitmask machinery in groups of at most 7 -- ops.seg_labelmap_to_bits, postprocess_mask on the group's bitmask, ops.seg_labelmap_keep, which turns
+    a voxel whose class lost its bit into background.  -> (label map, report [K]) with report[0] untouched."""
+    K, keep = int(K), {int(k) for k in keep_largest}
+    report = [{"before": None, "after": None, "removed": 0}]
+    for first in range(1, K, 7):
+        n = min(7, K - first)
+        bits = _ops.seg_labelmap_to_bits(lab, first, n)
+        bits, rep = postprocess_mask(bits, n, [k - first for k in keep if first <= k < first + n], min_voxels, connectivity)
+        lab = _ops.seg_labelmap_keep(lab, bits, first, n)
+        report.extend(rep)
+    return lab, report
+
+
+def _labelmap_classes(args, flag="--labelmap"):
+    """--labelmap: the stored arrays are label maps of --n_class classes, the background included (2..16)."""
+    return _data.check_n_class(args.n_class, "softmax")
+
+
+def _refuse_above(path, arr, K):
+    top = int((np.asarray(arr).reshape(-1) & 0x7F).max()) if arr.size else 0
+    if top >= K:
+        raise SystemExit(f"{path}: label value {top} but --n_class is {K} with --labelmap (a label-map byte holds the class index 0..{K - 1} in bits "
+                         "0..6, 0 = background)")
+
+
 def parse_cleanup(args):
     """--keep_largest, --min_voxels and --connectivity of `predict` and `postprocess` (absent attributes: the defaults), checked on the host.
     -> None when neither rule is given, else (keep, min_voxels, connectivity) with keep a tuple of classes or 'all' (resolve_keep)."""
@@ -435,7 +528,8 @@ def resolve_keep(keep, K):
 
 def postprocess_plan(args):
     """Everything `postprocess` refuses, checked on the host before a GPU is touched.  -> (K, (keep, min_voxels, connectivity), [(case, in, out)])"""
-    K = _data.check_n_class(args.n_class)
+    labelmap = bool(getattr(args, "labelmap", False))
+    K = _labelmap_classes(args) if labelmap else _data.check_n_class(args.n_class)
     rules = parse_cleanup(args)
     if rules is None:
         raise SystemExit("postprocess: no rule given: --keep_largest CLASSES|all and / or --min_voxels N")
@@ -450,6 +544,10 @@ def postprocess_plan(args):
         pred = np.load(path, mmap_mode="r")
         if pred.ndim != 3 or pred.dtype != np.uint8 or pred.size == 0 or pred.size >= 1 << 31:
             raise SystemExit(f"{path}: a prediction is a non-empty uint8 array [X, Y, Z] of fewer than 2^31 voxels, got {pred.dtype} {pred.shape}")
+        if labelmap:
+            _refuse_above(path, pred, K)
+        else:
+            refuse_labelmap_prediction(args.pred, "postprocess")
         plan.append((name, path, os.path.join(args.out, name + "_pred.npy")))
     if not plan:
         raise SystemExit(f"{args.list}: no cases")
@@ -464,11 +562,14 @@ def postprocess(args, log=print):
     os.makedirs(args.out, exist_ok=True)
     done = []
     for name, src, dst in plan:
-        mask, report = postprocess_mask(torch.from_numpy(np.load(src)).to(device), K, *rules)
+        clean = postprocess_labelmap if getattr(args, "labelmap", False) else postprocess_mask
+        mask, report = clean(torch.from_numpy(np.load(src)).to(device), K, *rules)
         np.save(dst, mask.cpu().numpy())
         done.append((name, report))
         log(name + "\t" + "\t".join("class {0}: components {1} -> {2}, {3} voxels removed".format(k, r["before"], r["after"], r["removed"])
                                     for k, r in enumerate(report) if r["before"] is not None))
+    if getattr(args, "labelmap", False):
+        write_head_kind(args.out, "softmax")
     log("Postprocess: {0} cases, connectivity {1}\t".format(len(plan), rules[2]) + "\t".join(
         "class {0}: {1} voxels removed".format(k, sum(rep[k]["removed"] for _, rep in done)) for k in range(K)))
     return done
@@ -554,7 +655,10 @@ def parse_spacing(spacing, what="--spacing"):
 
 def score_plan(args):
     """Everything `score` refuses, checked on the host before a GPU is touched.  -> [(case, seg path, pred path, spacing)]"""
-    K = _data.check_n_class(args.n_class)
+    labelmap = bool(getattr(args, "labelmap", False))
+    K = _labelmap_classes(args) if labelmap else _data.check_n_class(args.n_class)
+    if not labelmap:
+        refuse_labelmap_prediction(args.pred, "score")
     default = parse_spacing(args.spacing)
     plan = []
     for name in _data.read_list(args.data, args.list):
@@ -569,6 +673,9 @@ def score_plan(args):
             raise SystemExit(f"{seg_path}: expected a uint8 array [X, Y, Z], got {seg.dtype} {seg.shape}")
         if pred.dtype != np.uint8 or pred.shape != seg.shape:
             raise SystemExit(f"{pred_path}: a prediction is a uint8 array of its label's shape {seg.shape}, got {pred.dtype} {pred.shape}")
+        if labelmap:         # a value >= K is refused before the GPU is touched
+            _refuse_above(seg_path, seg, K)
+            _refuse_above(pred_path, pred, K)
         spacing = parse_spacing(np.load(sp_path), sp_path + ":") if os.path.exists(sp_path) else default
         plan.append((name, seg_path, pred_path, spacing))
     if not plan:
@@ -579,13 +686,16 @@ def score_plan(args):
 def score(args, log=print):
     """`seg3d.py score`: Dice, HD95, HD and ASSD per case and class of stored predictions.  -> the rows (case, class, dice, hd95, hd, assd, n_pred, n_gt)"""
     K, plan = score_plan(args)
+    labelmap = bool(getattr(args, "labelmap", False))
+    classes = list(range(1, K)) if labelmap else list(range(K))       # label maps: one row per (case, class 1..K-1); the background is not scored
     device = None
     rows = []
     for name, seg_path, pred_path, spacing in plan:
         cut = crop_to_masks(np.load(pred_path), np.load(seg_path))
         if cut is None:          # nothing predicted, nothing labelled: every class scores Dice 1 and distance 0 without a launch
-            m = {key: np.zeros(K) for key in SURFACE_KEYS}
-            m.update(n_pred=np.zeros(K, dtype=np.int64), n_gt=np.zeros(K, dtype=np.int64), counts=np.zeros((K, 3), dtype=np.int64))
+            nc = len(classes)
+            m = {key: np.zeros(nc) for key in SURFACE_KEYS}
+            m.update(n_pred=np.zeros(nc, dtype=np.int64), n_gt=np.zeros(nc, dtype=np.int64), counts=np.zeros((nc, 3), dtype=np.int64))
         else:
             if device is None:
                 device = torch.device("cuda", args.gpu)
@@ -593,14 +703,20 @@ def score(args, log=print):
             top = _ops.edt_max_axis()
             if max(cut[0].shape) > top:
                 raise SystemExit(f"{name}: the bounding box of its masks is {cut[0].shape}; an axis may have at most {top} voxels")
-            m = surface_metrics(torch.from_numpy(cut[0]).to(device), torch.from_numpy(cut[1]).to(device), K, spacing)
-        for k in range(K):
-            dice = dice_from_counts([[m["counts"][k].tolist()]])[1]
-            rows.append((name, k, dice, float(m["hd95"][k]), float(m["hd"][k]), float(m["assd"][k]), int(m["n_pred"][k]), int(m["n_gt"][k])))
+            pd, gd = torch.from_numpy(cut[0]).to(device), torch.from_numpy(cut[1]).to(device)
+            if labelmap:         # the classes 1..K-1 through the bitmask machinery, at most 7 at a time
+                parts = [surface_metrics(_ops.seg_labelmap_to_bits(pd, first, min(7, K - first)), _ops.seg_labelmap_to_bits(gd, first, min(7, K - first)),
+                                         min(7, K - first), spacing) for first in range(1, K, 7)]
+                m = {key: np.concatenate([p[key] for p in parts]) for key in parts[0]}
+            else:
+                m = surface_metrics(pd, gd, K, spacing)
+        for i, k in enumerate(classes):
+            dice = dice_from_counts([[m["counts"][i].tolist()]])[1]
+            rows.append((name, k, dice, float(m["hd95"][i]), float(m["hd"][i]), float(m["assd"][i]), int(m["n_pred"][i]), int(m["n_gt"][i])))
         log("{0}\tspacing {1}\t".format(name, ",".join("%g" % s for s in spacing)) + "\t".join(
-            "class {0}: Dice {1:.4f} HD95 {2:.3f} HD {3:.3f} ASSD {4:.3f}".format(*r[1:6]) for r in rows[-K:]))
+            "class {0}: Dice {1:.4f} HD95 {2:.3f} HD {3:.3f} ASSD {4:.3f}".format(*r[1:6]) for r in rows[-len(classes):]))
     means = []
-    for k in range(K):
+    for k in classes:
         part = ["class %d:" % k]
         for col, label in ((2, "Dice"), (3, "HD95"), (4, "HD"), (5, "ASSD")):
             vals = [r[col] for r in rows if r[1] == k and r[col] == r[col]]      # a NaN (one empty surface) is left out of the mean
