@@ -555,6 +555,37 @@ int pcrl_sgd_step_guarded(float* p, const float* g, float* buf, const int64_t* o
                           pcrl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Fine-tuning optimisers over the same arenas (csrc/optim.hip; offsets / flags as for pcrl_sgd_step, bit 0 alone is read): torch.optim.Adam /
+ * AdamW's single-tensor arithmetic in float32 with one rounding per operation, the global gradient norm with
+ * torch.nn.utils.clip_grad_norm_'s coefficient, and the SGD step with that coefficient.  pcrl_optim_grid_cap: the most blocks any of
+ * these streaming passes launches (256 threads x 4 elements each; the rest by grid stride).
+ *
+ * pcrl_adam_prepare (one thread per tensor, in front of the step): for every tensor with flag bit 0, steps[t] += 1,
+ * prods[2t] *= beta1, prods[2t + 1] *= beta2 (float64 running products beta^t, 1.0 before the first step),
+ * coefs[2t] = (float)(lr / (1 - beta1^t)), coefs[2t + 1] = (float)sqrt(1 - beta2^t); a tensor without a gradient keeps all of it.
+ * pcrl_adam_step, per element of a tensor with flag bit 0 (others keep p, m, v):
+ *   g' = (g * grad_scale) * clip_coef[0]            (clip_coef may be NULL: no second product)
+ *   decoupled: p = p * decay  [decay = (float)(1 - lr * wd)]      else: g' = g' + decay * p  [decay = wd]
+ *   m = m + (g' - m) * one_minus_beta1;   v = v * beta2 + (g' * g') * one_minus_beta2
+ *   p = p - coefs[2t] * (m / (sqrtf(v) / coefs[2t + 1] + eps))
+ * 16-byte accesses where a group of four lies inside one tensor and p, g, m, v are 16-byte aligned, scalar ones elsewhere.
+ * pcrl_grad_norm: norm[0] = sqrt(sum over the tensors with flag bit 0 of ((double)(g * grad_scale))^2), float64 in an order that depends on
+ * `total` alone (no atomics); numels (int64[ntensors], may be NULL) keeps a slot's padding out of the sum;
+ * coef[0] = (float)min(1, max_norm / (norm + 1e-6)); partials: float64[pcrl_optim_grid_cap()] of scratch.
+ * pcrl_sgd_step_clipped: pcrl_sgd_step on (g * grad_scale) * clip_coef[0]; with clip_coef[0] == 1 its result has pcrl_sgd_step's bits. */
+int pcrl_optim_grid_cap(void);
+int pcrl_adam_prepare(const int32_t* flags, int32_t* steps, double* prods, float* coefs, int ntensors, double lr, double beta1,
+                      double beta2, pcrl_stream_t stream);
+int pcrl_adam_step(float* p, const float* g, float* m, float* v, const int64_t* offsets, const int32_t* flags, const float* coefs,
+                   int ntensors, int64_t total, float decay, int decoupled, float one_minus_beta1, float beta2, float one_minus_beta2,
+                   float eps, float grad_scale, const float* clip_coef, pcrl_stream_t stream);
+int pcrl_grad_norm(const float* g, const int64_t* offsets, const int64_t* numels, const int32_t* flags, int ntensors, int64_t total,
+                   float grad_scale, double max_norm, double* partials, double* norm, float* coef, pcrl_stream_t stream);
+int pcrl_sgd_step_clipped(float* p, const float* g, float* buf, const int64_t* offsets, const int32_t* flags, int ntensors,
+                          int64_t total, float lr, float momentum, float weight_decay, float grad_scale, const float* clip_coef,
+                          pcrl_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Input pipeline: the torchio transforms of data.py:73-89 / datasets/lunaDataset.py:28-81 on float32 volumes
  * [B][D][H][W] resident on the device, one random parameter set per volume (drawn by the caller).  Each entry point states the definition
  * it implements and is pinned to it alone, bit for bit or to a derived bound (tests/test_augment_exact_gpu.py); the blur's definition is held

@@ -24,8 +24,9 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc",
 # reverse order fits all of them (profiles/r05_b16_isa_mix.txt).
 # augment2d.hip restates Pillow's and torch's CPU float arithmetic bit for bit, luna_prep.hip scipy's and ITK's float64 arithmetic,
 # luna_cubes.hip numpy's float64 normalisation, seg_blend.hip a float32 blend, surface_dist.hip a float64 distance transform and seg_prep.hip numpy's
-# float64 normalisation and scipy's trilinear zoom one operation at a time: no fused multiply-adds.
-FILE_FLAGS = {"augment2d.hip": ["-ffp-contract=off"], "luna_prep.hip": ["-ffp-contract=off"], "luna_cubes.hip": ["-ffp-contract=off"],
+# float64 normalisation and scipy's trilinear zoom one operation at a time: no fused multiply-adds.  optim.hip restates torch.optim.Adam's float32
+# arithmetic one operation at a time and writes out the few fused multiply-adds of its SGD step.
+FILE_FLAGS = {"optim.hip": ["-ffp-contract=off"], "augment2d.hip": ["-ffp-contract=off"], "luna_prep.hip": ["-ffp-contract=off"], "luna_cubes.hip": ["-ffp-contract=off"],
               "seg_blend.hip": ["-ffp-contract=off"], "surface_dist.hip": ["-ffp-contract=off"], "seg_prep.hip": ["-ffp-contract=off"],
               "conv_brick16.hip": ["-mllvm", "-greedy-reverse-local-assignment"], "conv_brick16_bnr.hip": ["-mllvm", "-greedy-reverse-local-assignment"],
               "conv_brick16_inf.hip": ["-mllvm", "-greedy-reverse-local-assignment"]}

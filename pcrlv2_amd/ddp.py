@@ -456,6 +456,8 @@ class DataParallel:
         dist.broadcast(self.opt.flat_p, src=0, group=self.group)
         if getattr(self.opt, "flat_buf", None) is not None:        # momentum buffers of a resumed run
             dist.broadcast(self.opt.flat_buf, src=0, group=self.group)
+        for t in getattr(self.opt, "_state_tensors", ()):           # FusedAdam / FusedAdamW: both moment arenas and the per-tensor step tables
+            dist.broadcast(t, src=0, group=self.group)
         for b in self.model.buffers():
             dist.broadcast(b, src=0, group=self.group)
 

@@ -23,6 +23,7 @@ from . import config as _cfg
 from . import ddp as _ddp
 from . import functions as _fn
 from . import ops as _ops
+from . import optim_cli as _optim_cli
 from .utils import AverageMeter, adjust_learning_rate
 
 
@@ -167,7 +168,7 @@ CHECKPOINT_KEYS = ('opt', 'state_dict', 'optimizer', 'epoch')       # the refere
 class Task:
     """What differs between the loops (DESIGN.md section 5 has the table).  The callables are looked up by the task's module when they run."""
     make_model: Callable         # (rank) -> the model; run_epochs calls .cuda() on it
-    make_optimizer: Callable     # (params, lr=, momentum=, weight_decay=)
+    make_optimizer: Callable     # (params, lr=, momentum=, weight_decay=[, kind=, betas=, eps=, max_grad_norm=])
     resume: Callable             # (path, model, optimizer, rank) -> the stored epoch
     resumed: str                 # rank 0's line after that: .format(path, first epoch)
     state_dict: Callable         # (model) -> what a checkpoint holds under 'state_dict'
@@ -195,7 +196,8 @@ def run_epochs(args, loaders, task, distributed):
     model = task.make_model(rank).cuda()
     if getattr(args, "amp", False):
         model.set_compute_dtype(torch.bfloat16)
-    optimizer = task.make_optimizer(model.parameters(), lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
+    optimizer = task.make_optimizer(model.parameters(), lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay,
+                                    **_optim_cli.options(args))      # --optimizer / --betas / --eps / --clip_grad; nothing more for plain SGD
     first_epoch = 0
     if getattr(args, "resume", None):       # BEFORE the data-parallel wrapper is built (module docstring)
         first_epoch = task.resume(args.resume, model, optimizer, rank) + 1

@@ -183,6 +183,8 @@ def extract(args, log=print):
 def train(args):
     if args.phase == "finetune" and not args.encoder_weights:
         raise SystemExit("--phase finetune needs --encoder_weights (a 3D pre-training checkpoint); to train the classifier from random weights use --phase scratch")
+    from . import optim_cli
+    optim_cli.check(args)
     from .main import launch
     launch(args)
     from .data import SyntheticNoduleLoader, nodule_loaders
@@ -289,6 +291,8 @@ def build_parser():
     tr.add_argument("--lr", type=float, default=1e-3)
     tr.add_argument("--momentum", type=float, default=0.9)
     tr.add_argument("--weight_decay", type=float, default=1e-4)
+    from . import optim_cli
+    optim_cli.add_arguments(tr)
     tr.add_argument("--ratio", type=float, default=0.8, help="fraction of train_val_txt/luna_train.txt used for PRE-training; the last 1 - ratio train here")
     tr.add_argument("--amp", action="store_true", help="bfloat16 activations and MFMA operands")
     tr.add_argument("--gpus", default="0", help="visible device ids, comma separated")

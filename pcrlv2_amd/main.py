@@ -63,6 +63,8 @@ def build_parser():
             ap.add_argument("--" + name, action="store_true", default=default, help=text)
         else:
             ap.add_argument("--" + name, default=default, type=kind, help=text)
+    from . import optim_cli
+    optim_cli.add_arguments(ap)       # --optimizer / --betas / --eps / --clip_grad: --d 2 --phase finetune | scratch only
     return ap
 
 
@@ -206,6 +208,10 @@ def check_route(args):
                          "random weights use --phase scratch")
     if args.d == 2 and supervised(args) and not 1 <= args.n_class <= 31:
         raise SystemExit("--n_class {}: 1..31".format(args.n_class))
+    from . import optim_cli
+    optim_cli.check(args)
+    if args.phase == 'pretask':
+        optim_cli.check_pretask(args)
 
 
 def launch(args):

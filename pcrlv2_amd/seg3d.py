@@ -66,6 +66,8 @@ def check_train(args):
     check_window(args.val_window, "--val_window")
     parse_mirror(args.val_mirror, "--val_mirror")
     parse_aug(args)
+    from . import optim_cli
+    optim_cli.check(args)
 
 
 def train(args):
@@ -147,6 +149,8 @@ def build_parser():
     tr.add_argument("--lr", type=float, default=1e-2)
     tr.add_argument("--momentum", type=float, default=0.9)
     tr.add_argument("--weight_decay", type=float, default=1e-4)
+    from . import optim_cli
+    optim_cli.add_arguments(tr)
     tr.add_argument("--gpus", default="0", help="visible device ids, comma separated")
     tr.add_argument("--amp", action="store_true", help="bfloat16 activations and MFMA operands")
     tr.add_argument("--val_every", type=int, default=0, help="validation after every N-th epoch; 0 = every epoch")

@@ -22,6 +22,7 @@ from . import ops2d as _ops2d
 from .functions2d import MaskMSEFn, SegMSEFn, mse_loss2d
 from .loop import to_gpu
 from .models.pcrlv2_model import PCRLv2
+from . import optim as _optim
 from .optim import FusedSGD
 from .train_3d import BETA_PERIOD, COS_MAX_TERMS, LOGGED, CosineSimilarityMean, cos_loss, fused_cos_losses  # noqa: F401  (cos_loss: train_2d.py:111-117)
 from .train_3d import lower_total, mean_scales, val_beta, val_text
@@ -152,7 +153,7 @@ def resume_encoder(path, model, optimizer, rank):
     ckpt = torch.load(path, map_location="cpu", weights_only=False)
     model.model.encoder.load_state_dict(ckpt["state_dict"])
     try:
-        optimizer.load_state_dict(ckpt["optimizer"])
+        _optim.restore(optimizer, ckpt)       # a checkpoint of another optimiser kind ends the run with a message
     except (ValueError, KeyError) as e:       # a checkpoint of another parameter list (group / size mismatch): keep fresh momentum, say so on EVERY rank
         print("==> [rank {}] optimizer state not restored: {}".format(rank, e))
     return int(ckpt.get("epoch", -1))

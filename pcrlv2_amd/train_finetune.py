@@ -22,6 +22,7 @@ from . import loop as _loop
 from . import ops2d as _ops2d
 from .loop import to_gpu
 from .models.pcrlv2_model import ChestClassifier
+from . import optim as _optim
 from .optim import FusedSGD
 
 
@@ -101,7 +102,7 @@ def resume_classifier(path, model, optimizer, rank):
     ckpt = torch.load(path, map_location="cpu", weights_only=False)
     model.load_state_dict(ckpt["state_dict"])
     if "optimizer" in ckpt:
-        optimizer.load_state_dict(ckpt["optimizer"])
+        _optim.restore(optimizer, ckpt)       # a checkpoint of another optimiser kind ends the run with a message
     return int(ckpt.get("epoch", -1))
 
 
@@ -138,7 +139,7 @@ def _train_classifier(args, loaders, make_model, key, distributed):
 
     task = _loop.Task(
         make_model=make,
-        make_optimizer=lambda *a, **k: FusedSGD(*a, **k),
+        make_optimizer=lambda params, **k: _optim.for_task(FusedSGD, params, **k),
         resume=resume_classifier,
         resumed="==> resumed the classifier from {}; continuing with epoch {}",
         state_dict=lambda model: model.state_dict(),

@@ -46,6 +46,7 @@ from . import loop as _loop
 from . import ops as _ops
 from .loop import to_gpu
 from .models import Segmenter3d
+from . import optim as _optim
 from .optim import FusedSGD
 from .seg_prep import lerp
 
@@ -261,7 +262,7 @@ def resume_segmenter(path, model, optimizer, rank):
     ckpt = torch.load(path, map_location="cpu", weights_only=False)
     model.load_state_dict(ckpt["state_dict"])
     if "optimizer" in ckpt:
-        optimizer.load_state_dict(ckpt["optimizer"])
+        _optim.restore(optimizer, ckpt)       # a checkpoint of another optimiser kind ends the run with a message
     return int(ckpt.get("epoch", -1))
 
 
@@ -292,7 +293,7 @@ def _train_segmenter(args, distributed):
 
     task = _loop.Task(
         make_model=make,
-        make_optimizer=lambda params, **k: FusedSGD([p for p in params if p.requires_grad], **k),      # only what the loss reaches: the heads are frozen
+        make_optimizer=lambda params, **k: _optim.for_task(FusedSGD, [p for p in params if p.requires_grad], **k),      # only what the loss reaches: the heads are frozen
         resume=resume_segmenter,
         resumed="==> resumed the segmenter from {}; continuing with epoch {}",
         state_dict=lambda model: model.state_dict(),
