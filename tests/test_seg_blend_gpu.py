@@ -10,6 +10,8 @@ blend    num, den, the mask and the integer counts EQUAL tests/seg_blend_referen
   sums   the head test's lines with E_z := |fl32(num32 / den32) - num64 / den64| + ULP |zbar|, the float32 restatement's own distance from the float64
          one plus the division: dp = E_z / 4 + 4 ULP p; E_P = sum dp, E_I = sum g dp (+ (M + 8) 2^-53 of the float64 sum); BCE_k: sum (E_z + 4 ULP |term|);
          loss: wb sum_k E_BCE_k / (Mc K) + (wd / K) sum_k (2 E_I / U + (2 I + eps) E_P / U^2) + 2 ULP |loss|.  G and Mc are exact.
+Every class count K = 1..7 is launched by the logits and the blend tests (1, 3, 7 with the whole lists, the others with compact ones), and the blend's
+loss takes unequal weights wb, wd in test_blend_loss_takes_its_weights_and_the_sums_do_not.
 """
 import os
 import sys
@@ -42,10 +44,10 @@ def _pack(z):
 
 
 # ---- logits -----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("K", [1, 3, 7])
+@pytest.mark.parametrize("K", H.ALL_KS)
 @H._DTYPES
 def test_logits_threshold_to_the_eval_mask_and_keep_the_head_bound(dtype, K):
-    for si, (N, sp) in enumerate(H.SHAPES):
+    for si, (N, sp) in enumerate(H.SHAPES if K in H.FULL_KS else H.REDUCED_SHAPES):
         a, w, b, lab = H._inputs(N, sp, K, dtype, "zeros", seed=900 * K + si)
         act = H._act(a, N, sp)
         z = ops.seg_head_logits(act, w.cuda(), b.cuda(), dtype)
@@ -60,10 +62,10 @@ def test_logits_threshold_to_the_eval_mask_and_keep_the_head_bound(dtype, K):
         assert bool((err <= e_z).all())
 
 
-@pytest.mark.parametrize("K", [1, 3, 7])
+@pytest.mark.parametrize("K", H.ALL_KS)
 @H._DTYPES
 def test_logits_equal_the_reference_on_exactly_summable_operands(dtype, K):
-    for N, sp in H.SHAPES:
+    for N, sp in H.SHAPES if K in H.FULL_KS else H.REDUCED_SHAPES:
         S = sp[0] * sp[1] * sp[2]
         a, w, b, lab = H._exact_inputs(N, sp, K, seed=31 * K + S)
         z = ops.seg_head_logits(H._act(a.to(dtype), N, sp), w.float().cuda(), b.float().cuda(), dtype)
@@ -159,8 +161,8 @@ def _dev(axes, weights):
     return ([torch.tensor(a, dtype=torch.int32, device=DEV) for a in axes], [torch.from_numpy(w).to(DEV) for w in weights])
 
 
-def _sum_bounds(zref32, zbar64, ref, K, M):
-    """The head test's E_P, E_I, BCE and loss lines with E_z as in the module docstring; flat [M, K] float64 inputs."""
+def _sum_bounds(zref32, zbar64, ref, K, M, wb=1.0, wd=1.0):
+    """The head test's E_P, E_I, BCE and loss lines with E_z as in the module docstring; flat [M, K] float64 inputs.  wb, wd: the weights of `ref`."""
     e_z = (torch.from_numpy(zref32).double() - zbar64).abs() + ULP * torch.from_numpy(zref32).double().abs()
     cnt = ref["counted"].double().unsqueeze(1)
     g, p = ref["g"], ref["p"]
@@ -169,11 +171,13 @@ def _sum_bounds(zref32, zbar64, ref, K, M):
     Uk, num, Mc = ref["P"] + ref["G"] + 1.0, 2 * ref["I"] + 1.0, ref["Mc"]
     e_bce = ((e_z + 4 * ULP * ref["terms"].abs()) * cnt).sum(0)
     sums = torch.cat([torch.stack([E_I, E_P, torch.zeros(K, dtype=torch.float64), e_bce], dim=1).reshape(-1), torch.zeros(1, dtype=torch.float64)])
-    loss = (e_bce.sum() / (Mc * K) if Mc else 0.0) + (1.0 / K) * (2 * E_I / Uk + num * E_P / Uk ** 2).sum() + 2 * ULP * ref["loss"].abs()
+    loss = (abs(wb) * e_bce.sum() / (Mc * K) if Mc else 0.0) + (abs(wd) / K) * (2 * E_I / Uk + num * E_P / Uk ** 2).sum() + 2 * ULP * ref["loss"].abs()
     return sums, loss
 
 
-def _check_blend(shape, K, overlap, window, zkind, label_kinds, seed, worst):
+def _check_blend(shape, K, overlap, window, zkind, label_kinds, seed, worst, weight_pairs=()):
+    """weight_pairs: further (wb, wd) the labelled runs are repeated with: the loss within its bound against the reference with those weights, the sums
+    the unit-weight run's bytes."""
     rng = np.random.default_rng(seed)
     axes, weights = D.windows(shape, CROP, overlap), D.blend_weights(CROP, window)
     z = _logits(zkind, axes, shape, K, rng)
@@ -236,6 +240,22 @@ def _check_blend(shape, K, overlap, window, zkind, label_kinds, seed, worst):
         worst["loss"] = max(worst.get("loss", 0.0), float(e_loss / t_loss.clamp_min(1e-300)))
         if kind == "all_off":
             assert not bool(mask.any()) and not bool(added.any()) and float(loss) == 0.0
+        seen = {}
+        for wb, wd in weight_pairs:
+            _, _, s_w, l_w, _ = ops.seg_blend(zd, sd, wd_, shape, labels=ld, want_mask=False, wb=wb, wd=wd)
+            torch.cuda.synchronize()
+            ref_w = reference(a, torch.eye(K, 64, dtype=torch.float64), torch.zeros(K, dtype=torch.float64), flat, 1.0, wb, wd)
+            _, t_w = _sum_bounds(zref32.reshape(-1, K), zbar64, ref_w, K, M, wb, wd)
+            e_w = (l_w.cpu().double() - ref_w["loss"]).abs()
+            assert s_w.cpu().numpy().tobytes() == sums.numpy().tobytes(), f"the sums do not depend on the weights ({wb}, {wd}): " + what
+            assert bool(e_w <= t_w), f"loss at weights ({wb}, {wd}): error {float(e_w):.3e} bound {float(t_w):.3e} " + what
+            worst["loss_w"] = max(worst.get("loss_w", 0.0), float(e_w / t_w.clamp_min(1e-300)))
+            if (wb, wd) == (0.0, 0.0):
+                assert float(l_w) == 0.0
+            seen[(wb, wd)] = (float(ref_w["loss"]), float(t_w))
+        if (0.25, 2.0) in seen and (2.0, 0.25) in seen and kind != "all_off":      # not vacuous: the swapped weights are another loss by far
+            assert abs(seen[(0.25, 2.0)][0] - seen[(2.0, 0.25)][0]) > 100 * seen[(0.25, 2.0)][1], what
+            assert abs(seen[(0.25, 2.0)][0] - float(ref["loss"])) > 100 * seen[(0.25, 2.0)][1], what
 
 
 @pytest.mark.parametrize("K", [1, 3, 7])
@@ -248,6 +268,22 @@ def test_blend_equals_the_float32_restatement_bit_for_bit(shape, K):
                 i += 1
                 _check_blend(shape, K, overlap, window, zkind, ("none", "mixed", "mixed30", "all_off"), 1000 * K + 10 * sum(shape) + i, worst)
     print(f"[seg_blend {shape} K={K}] worst error / bound: " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
+
+
+@pytest.mark.parametrize("K", [2, 4, 5, 6])
+def test_blend_at_the_other_class_counts(K):
+    """The instantiations the test above leaves out, compactly: a volume that is no multiple of the crop, overlapping gaussian windows."""
+    worst = {}
+    for i, zkind in enumerate(("random", "ties")):
+        _check_blend((9, 17, 13), K, 0.5, "gaussian", zkind, ("mixed30",), 5000 + 10 * K + i, worst)
+    print(f"[seg_blend compact K={K}] worst error / bound: " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
+
+
+def test_blend_loss_takes_its_weights_and_the_sums_do_not():
+    """wb, wd are arguments of pcrl_seg_blend (the loss of a blended case): the head test's weight pairs, same bound, the sums bit for bit."""
+    worst = {}
+    _check_blend((9, 17, 13), 3, 0.5, "gaussian", "random", ("mixed30",), 6003, worst, weight_pairs=H.WEIGHTS)
+    print("[seg_blend weights K=3] worst error / bound: " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
 
 
 @pytest.mark.parametrize("K,zkind", [(3, "random"), (3, "ties"), (7, "random"), (7, "ties")])

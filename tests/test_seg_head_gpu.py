@@ -17,6 +17,10 @@ Tolerances are derived, none is fitted (u = 2^-24, the float32 unit roundoff; UL
                                                                      one range of the second launch and its 4 ranges (+ 8 slack); computed from the launch
                                                                      geometry in _chain() below, which restates the header's description of the grid
 Uncounted voxels: exactly zero dx rows; all voxels uncounted: loss == wd * 0 and exactly zero dx, dW, db.
+Every class count the dispatch knows, K = 1..7, is launched in both dtypes by the reference, the exact-eval and (tests/test_seg_blend_gpu.py,
+tests/test_seg_mirror_gpu.py) the logits, accumulate and blend tests: FULL_KS with the whole shape and label lists, the others with REDUCED_SHAPES and
+REDUCED_LABELS.  The loss weights wb, wd enter _bounds exactly as the lines above state them, and test_unequal_loss_weights_* runs the kernels, the eval
+entry point and the autograd node with unequal ones: a swapped, dropped or doubled weight is invisible at (1, 1).
 The exact part draws a, W, b from exact_lattice's FINER lattice: every logit is exact in float32 in any order, so the integer counts and the predicted
 bitmask of the eval kernel must EQUAL the float64 reference's, ties at z = 0 included.
 """
@@ -40,9 +44,17 @@ pytestmark = pytest.mark.gpu
 U, ULP = 2.0 ** -24, 2.0 ** -23
 C = 64
 DLOSS = 0.75
-# M in {1, 63, 64, 257, 4099} as N x spatial
-SHAPES = [(1, (1, 1, 1)), (3, (1, 3, 7)), (1, (4, 4, 4)), (1, (1, 1, 257)), (1, (1, 4099, 1))]
+# M in {1, 63, 64, 257, 4099} as N x spatial, then N = 3 samples of S = 70 voxels: three blocks per sample, so both factors of the partial-block index
+# blockIdx.y * gridDim.x + blockIdx.x exceed 1
+SHAPES = [(1, (1, 1, 1)), (3, (1, 3, 7)), (1, (4, 4, 4)), (1, (1, 1, 257)), (1, (1, 4099, 1)), (3, (2, 5, 7))]
 LABELS = ("zeros", "ones", "mixed", "mixed30", "all_off")
+ALL_KS = [1, 2, 3, 4, 5, 6, 7]
+FULL_KS = (1, 3, 7)         # these run SHAPES x LABELS; the other class counts the lists below
+# less than one block's voxels with N = 3; gx = 3 with N = 3; nine blocks, the last one partial
+REDUCED_SHAPES = [(3, (1, 3, 7)), (3, (2, 5, 7)), (1, (1, 1, 257))]
+REDUCED_LABELS = ("mixed30", "all_off", "ones")
+WEIGHTS = [(0.25, 2.0), (2.0, 0.25), (0.0, 1.0), (1.0, 0.0), (0.0, 0.0)]      # all exact in float32
+WEIGHT_SHAPES = [(3, (2, 5, 7)), (1, (1, 1, 257))]
 _DTYPES = pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
 
 
@@ -74,10 +86,10 @@ def _act(a, N, sp):
     return a.cuda().view(N, sp[0], sp[1], sp[2], C).permute(0, 4, 1, 2, 3)
 
 
-def _run(a, w, b, lab, N, sp, dtype, dloss=DLOSS):
+def _run(a, w, b, lab, N, sp, dtype, dloss=DLOSS, wb=1.0, wd=1.0):
     ad, wd_, bd, ld = _act(a, N, sp), w.cuda(), b.cuda(), lab.cuda().view(N, *sp)
-    loss, sums = ops.seg_head_forward(ad, wd_, bd, ld, dtype)
-    dx, dw, db = ops.seg_head_backward(ad, wd_, bd, ld, sums, torch.tensor(dloss, device="cuda"), dtype)
+    loss, sums = ops.seg_head_forward(ad, wd_, bd, ld, dtype, wb, wd)
+    dx, dw, db = ops.seg_head_backward(ad, wd_, bd, ld, sums, torch.tensor(dloss, device="cuda"), dtype, wb, wd)
     torch.cuda.synchronize()
     return dict(loss=loss.cpu(), sums=sums.cpu(), dx=dx.permute(0, 2, 3, 4, 1).reshape(-1, C).cpu(), dw=dw.cpu(), db=db.cpu())
 
@@ -89,7 +101,8 @@ def _chain(N, S, dtype):
     return per_lane + 8 + -(-(gx * N) // 4) + 4 + 8
 
 
-def _bounds(a, w, b, ref, K, N, S, dtype, dloss):
+def _bounds(a, w, b, ref, K, N, S, dtype, dloss, wb=1.0, wd=1.0):
+    """The module docstring's lines; `ref` is the reference computed with the same wb, wd."""
     A, W = a.double().abs(), w.double().abs()
     cnt = ref["counted"].double().unsqueeze(1)
     g, p = ref["g"], ref["p"]
@@ -102,10 +115,10 @@ def _bounds(a, w, b, ref, K, N, S, dtype, dloss):
     Mc = ref["Mc"]
     e_bce = ((e_z + 4 * ULP * ref["terms"].abs()) * cnt).sum(0)
     t["sums"] = torch.cat([torch.stack([E_I, E_P, torch.zeros(K, dtype=torch.float64), e_bce], dim=1).reshape(-1), torch.zeros(1, dtype=torch.float64)])
-    t["loss"] = (e_bce.sum() / (Mc * K) if Mc else 0.0) + (1.0 / K) * (2 * E_I / Uk + num * E_P / Uk ** 2).sum() + 2 * ULP * ref["loss"].abs()
+    t["loss"] = (abs(wb) * e_bce.sum() / (Mc * K) if Mc else 0.0) + (abs(wd) / K) * (2 * E_I / Uk + num * E_P / Uk ** 2).sum() + 2 * ULP * ref["loss"].abs()
     c = abs(dloss)
-    cA = c / (Mc * K) if Mc else 0.0
-    cd = c / K
+    cA = c * abs(wb) / (Mc * K) if Mc else 0.0
+    cd = c * abs(wd) / K
     e1, e0 = cd * 2 / Uk, cd * num / Uk ** 2
     de1, de0 = e1 * E_P / Uk, cd * (2 * E_I / Uk ** 2 + 2 * num * E_P / Uk ** 3)
     e_dz = ((cA + (g * e1 - e0).abs()) * dp + (g * de1 + de0) / 4 + 8 * U * (cA + g * e1 + e0)) * cnt          # [M, K]
@@ -120,13 +133,14 @@ def _bounds(a, w, b, ref, K, N, S, dtype, dloss):
     return t
 
 
-@pytest.mark.parametrize("K", [1, 3, 7])
+@pytest.mark.parametrize("K", ALL_KS)
 @_DTYPES
 def test_head_and_loss_against_float64_restatement(dtype, K):
     worst = {}
-    for si, (N, sp) in enumerate(SHAPES):
+    shapes, labels = (SHAPES, LABELS) if K in FULL_KS else (REDUCED_SHAPES, REDUCED_LABELS)
+    for si, (N, sp) in enumerate(shapes):
         S = sp[0] * sp[1] * sp[2]
-        for li, kind in enumerate(LABELS):
+        for li, kind in enumerate(labels):
             a, w, b, lab = _inputs(N, sp, K, dtype, kind, seed=10000 * K + 100 * si + 10 * li + (dtype == torch.bfloat16))
             ref = reference(a, w, b, lab, DLOSS)
             got = _run(a, w, b, lab, N, sp, dtype)
@@ -147,20 +161,22 @@ def test_head_and_loss_against_float64_restatement(dtype, K):
 
 @_DTYPES
 def test_capped_grid_where_a_lane_walks_several_voxels(dtype):
-    """S > 32768: the grid is capped at 1024 blocks, every lane takes more than one voxel (the prefetching loop) -- same bounds."""
-    N, sp, K = 1, (3, 7, 1829), 3
+    """S > 32768: the grid is capped at 1024 blocks, every lane takes more than one voxel (the prefetching loop) -- same bounds.  K = 3, and K = 6
+    (an instantiation the uncapped lists reach with their reduced shapes only)."""
+    N, sp = 1, (3, 7, 1829)
     S = sp[0] * sp[1] * sp[2]
-    a, w, b, lab = _inputs(N, sp, K, dtype, "mixed30", seed=77)
-    ref = reference(a, w, b, lab, DLOSS)
-    got = _run(a, w, b, lab, N, sp, dtype)
-    tol = _bounds(a, w, b, ref, K, N, S, dtype, DLOSS)
-    for name in ("sums", "loss", "dx", "dw", "db"):
-        err = (got[name].double() - ref[name]).abs()
-        print(f"[seg_head capped {dtype}] {name}: worst error / bound {float((err / tol[name].clamp_min(1e-300)).max()):.3f}")
-        assert bool((err <= tol[name]).all()), name
+    for K in (3, 6):
+        a, w, b, lab = _inputs(N, sp, K, dtype, "mixed30", seed=77 if K == 3 else 77 + K)
+        ref = reference(a, w, b, lab, DLOSS)
+        got = _run(a, w, b, lab, N, sp, dtype)
+        tol = _bounds(a, w, b, ref, K, N, S, dtype, DLOSS)
+        for name in ("sums", "loss", "dx", "dw", "db"):
+            err = (got[name].double() - ref[name]).abs()
+            print(f"[seg_head capped {dtype} K={K}] {name}: worst error / bound {float((err / tol[name].clamp_min(1e-300)).max()):.3f}")
+            assert bool((err <= tol[name]).all()), f"{name} K={K}"
 
 
-def _exact_inputs(N, sp, K, seed):
+def _exact_inputs(N, sp, K, seed, kind="mixed30"):
     g = torch.Generator().manual_seed(seed)
     M = N * sp[0] * sp[1] * sp[2]
     a = lattice((M, C), *FINER["x"], g)
@@ -169,15 +185,21 @@ def _exact_inputs(N, sp, K, seed):
     b[0] = 0.0
     a[::5] = 0.0                      # whole zero rows: z_0 = 0 exactly, a tie that must be predicted (z >= 0)
     assert_exactly_summable(a.abs() @ w.abs().t() + b.abs(), unit(FINER["x"][1], FINER["w"][1]), "seg head logits")
-    return a, w, b, _labels("mixed30", M, K, g)
+    return a, w, b, _labels(kind, M, K, g)
 
 
-@pytest.mark.parametrize("K", [1, 3, 7])
+EVAL_CASES = [(1, (1, 1, 1), None, 1), (3, (1, 3, 7), [1, 0, 1], 2), (1, (1, 1, 257), [2], 3), (3, (5, 13, 21), [1, 0, 1], 2), (1, (1, 4099, 1), None, 1),
+              (3, (2, 5, 7), [1, 0, 1], 2)]
+REDUCED_EVAL_CASES = [(3, (1, 3, 7), [1, 0, 1], 2), (3, (2, 5, 7), [1, 0, 1], 2), (1, (1, 1, 257), [2], 3)]
+
+
+@pytest.mark.parametrize("K", ALL_KS)
 @_DTYPES
 def test_eval_counts_and_mask_equal_the_reference_on_exactly_summable_operands(dtype, K):
-    for N, sp, ci, n_cases in [(1, (1, 1, 1), None, 1), (3, (1, 3, 7), [1, 0, 1], 2), (1, (1, 1, 257), [2], 3), (3, (5, 13, 21), [1, 0, 1], 2), (1, (1, 4099, 1), None, 1)]:
+    cases, kinds = (EVAL_CASES, ("mixed30",)) if K in FULL_KS else (REDUCED_EVAL_CASES, REDUCED_LABELS)
+    for (N, sp, ci, n_cases), kind in [(c, k) for c in cases for k in kinds]:
         S = sp[0] * sp[1] * sp[2]
-        a, w, b, lab = _exact_inputs(N, sp, K, seed=31 * K + S)
+        a, w, b, lab = _exact_inputs(N, sp, K, seed=31 * K + S, kind=kind)
         ref = reference(a, w, b, lab, case_index=ci, n_cases=n_cases, S=S)
         assert int((ref["z"] == 0).sum()) > 0 or S == 1, "the case list must contain ties at z = 0"
         cid = None if ci is None else torch.tensor(ci, dtype=torch.int32, device="cuda")
@@ -185,8 +207,8 @@ def test_eval_counts_and_mask_equal_the_reference_on_exactly_summable_operands(d
         out = ops.seg_head_eval(_act(a.to(dtype), N, sp), w.float().cuda(), b.float().cuda(), dtype, labels=lab.cuda().view(N, *sp), case_index=cid,
                                 counts=counts, want_mask=True)
         torch.cuda.synchronize()
-        assert out[0] is counts and torch.equal(counts.cpu(), ref["counts"]), f"counts differ at N={N} spatial={sp} K={K}"
-        assert torch.equal(out[3].reshape(-1).cpu(), ref["mask"]), f"mask differs at N={N} spatial={sp} K={K}"
+        assert out[0] is counts and torch.equal(counts.cpu(), ref["counts"]), f"counts differ at N={N} spatial={sp} K={K} labels={kind}"
+        assert torch.equal(out[3].reshape(-1).cpu(), ref["mask"]), f"mask differs at N={N} spatial={sp} K={K} labels={kind}"
         assert torch.equal(out[2].cpu()[2:4 * K:4], ref["G"]) and float(out[2][4 * K]) == ref["Mc"]
         # a second call ADDS to the table
         ops.seg_head_eval(_act(a.to(dtype), N, sp), w.float().cuda(), b.float().cuda(), dtype, labels=lab.cuda().view(N, *sp), case_index=cid, counts=counts)
@@ -273,15 +295,91 @@ def test_autograd_node_hands_over_the_raw_calls_gradients(dtype):
     from pcrlv2_amd import functions as Fn
     N, sp, K = 3, (2, 3, 7), 3
     a, w, b, lab = _inputs(N, sp, K, dtype, "mixed30", seed=11)
-    raw = _run(a, w, b, lab, N, sp, dtype, dloss=1.0)
-    ad = _act(a, N, sp).requires_grad_(True)
-    wp, bp = torch.nn.Parameter(w.cuda().view(K, C, 1, 1, 1)), torch.nn.Parameter(b.cuda())
-    mod = types.SimpleNamespace(compute_dtype=dtype, _pass_idx=1)
-    Fn.reset_parked()
-    loss, sums = Fn.SegHeadFn.apply(ad, wp, bp, lab.cuda().view(N, *sp), 1.0, 1.0, mod)
-    assert loss.requires_grad and not sums.requires_grad
-    loss.backward()
+    seen = []
+    for wb, wd in ((1.0, 1.0), (0.25, 2.0)):
+        raw = _run(a, w, b, lab, N, sp, dtype, dloss=1.0, wb=wb, wd=wd)
+        ad = _act(a, N, sp).requires_grad_(True)
+        wp, bp = torch.nn.Parameter(w.cuda().view(K, C, 1, 1, 1)), torch.nn.Parameter(b.cuda())
+        mod = types.SimpleNamespace(compute_dtype=dtype, _pass_idx=1)
+        Fn.reset_parked()
+        loss, sums = Fn.SegHeadFn.apply(ad, wp, bp, lab.cuda().view(N, *sp), wb, wd, mod)
+        assert loss.requires_grad and not sums.requires_grad
+        loss.backward()
+        torch.cuda.synchronize()
+        assert torch.equal(loss.detach().cpu(), raw["loss"]) and torch.equal(sums.cpu(), raw["sums"])
+        assert torch.equal(_bits(ad.grad.permute(0, 2, 3, 4, 1).reshape(-1, C).cpu()), _bits(raw["dx"]))
+        assert torch.equal(wp.grad.view(K, C).cpu(), raw["dw"]) and torch.equal(bp.grad.cpu(), raw["db"])
+        seen.append(raw)
+    assert not torch.equal(seen[0]["loss"], seen[1]["loss"]) and not torch.equal(seen[0]["dw"], seen[1]["dw"]), "the weights reach the loss and the gradients"
+
+
+def _gap(x, y, tol):
+    """Whether x and y differ by more than 100 x the bound somewhere: the weights under test are far from the ones they could be mistaken for."""
+    return bool(((x - y).abs() > 100 * tol).any())
+
+
+@pytest.mark.parametrize("K", [1, 4, 7])
+@_DTYPES
+def test_unequal_loss_weights_against_float64_restatement(dtype, K):
+    """wb and wd multiply the two loss terms in the second launch of the forward and are folded into cA, e1, e0 of the backward; at (1, 1) a swap, a
+    weight left out or one applied twice cannot be seen.  Bounds as above with the weights in them.  On top: the sums do not depend on the weights (bit for
+    bit); at (0, 0) everything is exactly zero; the eval entry point's loss is the forward's bit for bit.  The test is not vacuous: at (0.25, 2.0) the
+    REFERENCE's loss, dW and db are further than 100 x the bound from the references with the weights swapped and with unit weights."""
+    worst = {}
+    for si, (N, sp) in enumerate(WEIGHT_SHAPES):
+        S = sp[0] * sp[1] * sp[2]
+        a, w, b, lab = _inputs(N, sp, K, dtype, "mixed30", seed=20000 * K + 100 * si + (dtype == torch.bfloat16))
+        ad, wdev, bdev, ld = _act(a, N, sp), w.cuda(), b.cuda(), lab.cuda().view(N, *sp)
+        unit_sums = _run(a, w, b, lab, N, sp, dtype)["sums"]
+        for wb, wd in WEIGHTS:
+            where = f"at N={N} spatial={sp} K={K} wb={wb} wd={wd} {dtype}"
+            ref = reference(a, w, b, lab, DLOSS, wb, wd)
+            got = _run(a, w, b, lab, N, sp, dtype, wb=wb, wd=wd)
+            tol = _bounds(a, w, b, ref, K, N, S, dtype, DLOSS, wb, wd)
+            assert torch.equal(_bits(got["sums"]), _bits(unit_sums)), "the sums do not depend on the weights " + where
+            for name in ("sums", "loss", "dx", "dw", "db"):
+                err = (got[name].double() - ref[name]).abs()
+                ratio = float((err / tol[name].clamp_min(1e-300)).max()) if float(err.max()) > 0 else 0.0
+                worst[name] = max(worst.get(name, 0.0), ratio)
+                assert bool((err <= tol[name]).all()), f"{name}: error / bound = {ratio:.3f} {where}"
+            if (wb, wd) == (0.0, 0.0):
+                assert float(got["loss"]) == 0.0 and not bool(got["dx"].float().abs().any()) and not bool(got["dw"].abs().any()) and not bool(got["db"].abs().any())
+            if (wb, wd) == (0.25, 2.0):
+                for other in (reference(a, w, b, lab, DLOSS, wd, wb), reference(a, w, b, lab, DLOSS, 1.0, 1.0)):
+                    for name in ("loss", "dw", "db"):
+                        assert _gap(ref[name], other[name], tol[name]), f"{name}: the reference does not tell these weights from others {where}"
+            out = ops.seg_head_eval(ad, wdev, bdev, dtype, labels=ld, wb=wb, wd=wd)
+            torch.cuda.synchronize()
+            assert torch.equal(_bits(out[1].cpu()), _bits(got["loss"])) and torch.equal(_bits(out[2].cpu()), _bits(got["sums"])), "eval " + where
+    print(f"[seg_head weights {dtype} K={K}] worst error / bound: " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
+
+
+@_DTYPES
+def test_bce_alone_still_moves_a_class_without_ground_truth(dtype):
+    """wd = 0, K = 1, no voxel of the class anywhere: the Dice term is gone and G = 0, the BCE gradient cA (p - 0) is not."""
+    N, sp, K = 3, (2, 5, 7), 1
+    S = sp[0] * sp[1] * sp[2]
+    a, w, b, lab = _inputs(N, sp, K, dtype, "zeros", seed=23)
+    ref = reference(a, w, b, lab, DLOSS, 1.0, 0.0)
+    got = _run(a, w, b, lab, N, sp, dtype, wb=1.0, wd=0.0)
+    tol = _bounds(a, w, b, ref, K, N, S, dtype, DLOSS, 1.0, 0.0)
+    assert float(got["sums"][2]) == 0.0 and float(ref["db"].abs().min()) > 100 * float(tol["db"].max()) and float(got["db"].abs().min()) > 0.0
+    for name in ("sums", "loss", "dx", "dw", "db"):
+        err = (got[name].double() - ref[name]).abs()
+        print(f"[seg_head bce alone {dtype}] {name}: worst error / bound {float((err / tol[name].clamp_min(1e-300)).max()):.3f}")
+        assert bool((err <= tol[name]).all()), name
+
+
+@_DTYPES
+def test_backward_without_dx_leaves_dw_and_db_as_they_are(dtype):
+    """need_dx=False hands the kernel a null dx: no dx comes back, dW and db are the bytes of the run that wrote one."""
+    N, sp, K = 3, (2, 5, 7), 3
+    a, w, b, lab = _inputs(N, sp, K, dtype, "mixed30", seed=13)
+    ad, wdev, bdev, ld = _act(a, N, sp), w.cuda(), b.cuda(), lab.cuda().view(N, *sp)
+    loss, sums = ops.seg_head_forward(ad, wdev, bdev, ld, dtype)
+    dl = torch.tensor(DLOSS, device="cuda")
+    dx, dw, db = ops.seg_head_backward(ad, wdev, bdev, ld, sums, dl, dtype)
+    none, dw2, db2 = ops.seg_head_backward(ad, wdev, bdev, ld, sums, dl, dtype, need_dx=False)
     torch.cuda.synchronize()
-    assert torch.equal(loss.detach().cpu(), raw["loss"]) and torch.equal(sums.cpu(), raw["sums"])
-    assert torch.equal(_bits(ad.grad.permute(0, 2, 3, 4, 1).reshape(-1, C).cpu()), _bits(raw["dx"]))
-    assert torch.equal(wp.grad.view(K, C).cpu(), raw["dw"]) and torch.equal(bp.grad.cpu(), raw["db"])
+    assert none is None and dx is not None and bool(dw.abs().sum() > 0)
+    assert torch.equal(_bits(dw), _bits(dw2)) and torch.equal(_bits(db), _bits(db2))

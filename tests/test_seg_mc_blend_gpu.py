@@ -7,6 +7,8 @@ Derived, none fitted (u = 2^-24, ULP = 2^-23): zbar_k = num_k / den is one corre
 ULP |zref32| of zref32 = n32 / d32.  Against the float64 blend zbar64 the logit error is  E_z = |zref32 - zbar64| + ULP |zref32|,  and the probabilities,
 sums and loss follow tests/test_seg_mc_head_gpu.py's lines with that E_z (forward_bounds), the sum s taken serially over the K classes (K - 1 additions
 instead of the head's butterfly).  The float64 reference is the head's, fed with zbar64 as its logits (unit weight rows, zero bias).
+Every class count K = 2..16 is launched (2, 9, 16 with the whole lists, the others compactly), and the blend's loss takes unequal weights wc, wd in
+test_label_map_blend_loss_takes_its_weights_and_the_sums_do_not.
 """
 import os
 import sys
@@ -24,7 +26,7 @@ from pcrlv2_amd import ops  # noqa: E402
 from pcrlv2_amd._lib import PcrlError  # noqa: E402
 from seg_blend_reference import blend32, blend64  # noqa: E402
 from seg_mc_reference import reference  # noqa: E402
-from test_seg_mc_head_gpu import ULP, forward_bounds  # noqa: E402
+from test_seg_mc_head_gpu import ULP, WEIGHTS, forward_bounds  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 CROP = (8, 8, 8)
@@ -72,7 +74,9 @@ def _counts_of(pred, lab, K):
     return out
 
 
-def _check(shape, K, overlap, window, zkind, label_kinds, seed, worst):
+def _check(shape, K, overlap, window, zkind, label_kinds, seed, worst, weight_pairs=()):
+    """weight_pairs: further (wc, wd) the labelled runs are repeated with: the loss within its bound against the reference with those weights, the sums
+    the unit-weight run's bytes."""
     rng = np.random.default_rng(seed)
     axes, weights = D.windows(shape, CROP, overlap), D.blend_weights(CROP, window)
     z = _logits(zkind, axes, shape, K, rng)
@@ -134,6 +138,22 @@ def _check(shape, K, overlap, window, zkind, label_kinds, seed, worst):
         worst["loss"] = max(worst.get("loss", 0.0), float(e_loss / tol["loss"].clamp_min(1e-300)))
         if kind == "all_off":
             assert not bool(lm.any()) and not bool(added.any()) and float(loss) == 0.0
+        seen = {}
+        for wc, wd in weight_pairs:
+            _, _, s_w, l_w, _ = ops.seg_mc_blend(zd, sd, wd_, shape, labels=ld, want_mask=False, wc=wc, wd=wd)
+            torch.cuda.synchronize()
+            ref_w = reference(a, torch.eye(K, 64, dtype=torch.float64), torch.zeros(K, dtype=torch.float64), flat, 1.0, wc, wd)
+            t_w = forward_bounds(e_z, ref_w, K, M, s_adds=K - 1, wc=wc, wd=wd)["loss"]
+            e_w = (l_w.cpu().double() - ref_w["loss"]).abs()
+            assert s_w.cpu().numpy().tobytes() == sums.numpy().tobytes(), f"the sums do not depend on the weights ({wc}, {wd}): " + what
+            assert bool(e_w <= t_w), f"loss at weights ({wc}, {wd}): error {float(e_w):.3e} bound {float(t_w):.3e} " + what
+            worst["loss_w"] = max(worst.get("loss_w", 0.0), float(e_w / t_w.clamp_min(1e-300)))
+            if (wc, wd) == (0.0, 0.0):
+                assert float(l_w) == 0.0
+            seen[(wc, wd)] = (float(ref_w["loss"]), float(t_w))
+        if (0.25, 2.0) in seen and (2.0, 0.25) in seen and kind != "all_off":      # not vacuous: the swapped weights are another loss by far
+            assert abs(seen[(0.25, 2.0)][0] - seen[(2.0, 0.25)][0]) > 100 * seen[(0.25, 2.0)][1], what
+            assert abs(seen[(0.25, 2.0)][0] - float(ref["loss"])) > 100 * seen[(0.25, 2.0)][1], what
 
 
 @pytest.mark.parametrize("K", [2, 9, 16])
@@ -146,6 +166,22 @@ def test_label_map_blend_equals_the_float32_restatement_bit_for_bit(shape, K):
                 i += 1
                 _check(shape, K, overlap, window, zkind, ("none", "mixed", "mixed30", "all_off"), 1000 * K + 10 * sum(shape) + i, worst)
     print(f"[seg_mc_blend {shape} K={K}] worst error / bound: " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
+
+
+@pytest.mark.parametrize("K", [k for k in range(2, 17) if k not in (2, 9, 16)])
+def test_label_map_blend_at_the_other_class_counts(K):
+    """The instantiations the test above leaves out, compactly: a volume that is no multiple of the crop, overlapping gaussian windows."""
+    worst = {}
+    for i, zkind in enumerate(("random", "ties")):
+        _check((9, 17, 13), K, 0.5, "gaussian", zkind, ("mixed30",), 5000 + 10 * K + i, worst)
+    print(f"[seg_mc_blend compact K={K}] worst error / bound: " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
+
+
+def test_label_map_blend_loss_takes_its_weights_and_the_sums_do_not():
+    """wc, wd are arguments of pcrl_seg_mc_blend (the loss of a blended case): the head test's weight pairs, same bound, the sums bit for bit."""
+    worst = {}
+    _check((9, 17, 13), 5, 0.5, "gaussian", "random", ("mixed30",), 6005, worst, weight_pairs=WEIGHTS)
+    print("[seg_mc_blend weights K=5] worst error / bound: " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
 
 
 def test_outputs_are_optional_and_bad_arguments_are_refused():

@@ -138,6 +138,22 @@ def test_head_and_class_count_refusals_of_train():
     seg3d.check_train(_train_args("--n_class", "7"))
 
 
+def test_train_builds_its_model_with_the_parsed_head_and_ce_weight():
+    """`seg3d.py train --head softmax --wc 0.5`: the model train_seg hands to the epoch loop carries that head and that weight (the loop itself and the
+    data are replaced: no device is needed to construct the model)."""
+    from pcrlv2_amd import train_seg as T
+    args = _train_args("--head", "softmax", "--wc", "0.5", "--n_class", "4")
+    orig = T._loop.run_epochs, T._data.loaders
+    try:
+        T._data.loaders = lambda *a, **k: {}
+        T._loop.run_epochs = lambda args, loaders, task, distributed: (task.make_model(0), None, False)
+        model = T._train_segmenter(args, False)
+    finally:
+        T._loop.run_epochs, T._data.loaders = orig
+    assert (model.head, model.wc, model.wd, model.wb, model.n_class) == ("softmax", 0.5, 1.0, 1.0, 4)
+    assert T._loop.run_epochs is orig[0] and T._data.loaders is orig[1]
+
+
 def test_default_parser_values_are_unchanged():
     a = _train_args()
     assert (a.head, a.wc, a.n_class, a.in_channels, a.crop, a.b, a.val_overlap, a.val_mirror) == ("sigmoid", 1.0, 3, 1, "64,64,32", 8, 0.0, "none")

@@ -25,6 +25,12 @@ Tolerances are derived, none is fitted (u = 2^-24, the float32 unit roundoff; UL
                                                               of the second launch and its 4 ranges (+ 8 slack); _chain() restates the launch geometry,
                                                               which is the sigmoid head's (tests/test_seg_head_gpu.py)
 Uncounted voxels: exactly zero dx rows; all voxels uncounted: loss == 0 and exactly zero dx, dW, db.
+Every class count the dispatch knows, K = 2..16, is launched in both dtypes by the reference, the exact-eval, the logits and the mirror tests here and by
+tests/test_seg_mc_blend_gpu.py: KS with the whole shape and label lists, the others with REDUCED_SHAPES and REDUCED_LABELS.  The geometry changes with K
+(McGeom in csrc/seg_head_mc.hip: KP = K rounded up to a power of two, CPL classes per lane, DUP lanes per class), and the padded classes K..KP-1 stay out
+of the max, the sum, the argmin and the partial slots by guards alone, so every padding count matters.  The loss weights wc, wd enter forward_bounds and
+_bounds exactly as the lines above state them, and test_unequal_loss_weights_* runs the kernels, the eval entry point and the autograd node with unequal
+ones: a swapped, dropped or doubled weight is invisible at (1, 1).
 The exact part draws a, W, b from exact_lattice's FINER lattice: every logit is exact in float32 in any order, so the maximum, its ties, the integer
 counts and the predicted label map of the eval kernel must EQUAL the float64 reference's (lowest index among the tied classes).
 """
@@ -50,10 +56,18 @@ pytestmark = pytest.mark.gpu
 U, ULP = 2.0 ** -24, 2.0 ** -23
 C = 64
 DLOSS = 0.75
-KS = [2, 3, 8, 9, 16]       # the minimum, a non-power of two, bf16's lanes per voxel, one above it, the maximum
-# M in {1, 63, 64, 257, 4099} as N x spatial
-SHAPES = [(1, (1, 1, 1)), (3, (1, 3, 7)), (1, (4, 4, 4)), (1, (1, 1, 257)), (1, (1, 4099, 1))]
+KS = [2, 3, 8, 9, 16]       # the minimum, a non-power of two, bf16's lanes per voxel, one above it, the maximum: the whole shape and label lists
+ALL_KS = list(range(2, 17))  # every instantiation; those not in KS run the reduced lists: 4 (KP == K, DUP = 4 / 2), 5..7 (KP = 8, padded), 10..15 (KP = 16,
+#                              padded; at 15 the one padded class shares a lane with class 14 in bf16, where CPL = 2)
+# M in {1, 63, 64, 257, 4099} as N x spatial, then N = 3 samples of S = 70 voxels: three blocks per sample, so both factors of the partial-block index
+# blockIdx.y * gridDim.x + blockIdx.x exceed 1
+SHAPES = [(1, (1, 1, 1)), (3, (1, 3, 7)), (1, (4, 4, 4)), (1, (1, 1, 257)), (1, (1, 4099, 1)), (3, (2, 5, 7))]
 LABELS = ("background", "one_class", "mixed", "mixed30", "all_off")
+# less than one block's voxels with N = 3; gx = 3 with N = 3; nine blocks, the last one partial
+REDUCED_SHAPES = [(3, (1, 3, 7)), (3, (2, 5, 7)), (1, (1, 1, 257))]
+REDUCED_LABELS = ("mixed30", "all_off", "one_class")
+WEIGHTS = [(0.25, 2.0), (2.0, 0.25), (0.0, 1.0), (1.0, 0.0), (0.0, 0.0)]      # all exact in float32
+WEIGHT_SHAPES = [(3, (2, 5, 7)), (1, (1, 1, 257))]
 _DTYPES = pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
 
 
@@ -84,10 +98,10 @@ def _act(a, N, sp):
     return a.cuda().view(N, sp[0], sp[1], sp[2], C).permute(0, 4, 1, 2, 3)
 
 
-def _run(a, w, b, lab, N, sp, dtype, dloss=DLOSS):
+def _run(a, w, b, lab, N, sp, dtype, dloss=DLOSS, wc=1.0, wd=1.0):
     ad, wd_, bd, ld = _act(a, N, sp), w.cuda(), b.cuda(), lab.cuda().view(N, *sp)
-    loss, sums = ops.seg_mc_head_forward(ad, wd_, bd, ld, dtype)
-    dx, dw, db = ops.seg_mc_head_backward(ad, wd_, bd, ld, sums, torch.tensor(dloss, device="cuda"), dtype)
+    loss, sums = ops.seg_mc_head_forward(ad, wd_, bd, ld, dtype, wc, wd)
+    dx, dw, db = ops.seg_mc_head_backward(ad, wd_, bd, ld, sums, torch.tensor(dloss, device="cuda"), dtype, wc, wd)
     torch.cuda.synchronize()
     return dict(loss=loss.cpu(), sums=sums.cpu(), dx=dx.permute(0, 2, 3, 4, 1).reshape(-1, C).cpu(), dw=dw.cpu(), db=db.cpu())
 
@@ -99,9 +113,10 @@ def _chain(N, S, dtype):
     return per_lane + 8 + -(-(gx * N) // 4) + 4 + 8
 
 
-def forward_bounds(e_z, ref, K, M, s_adds=5):
+def forward_bounds(e_z, ref, K, M, s_adds=5, wc=1.0, wd=1.0):
     """The docstring's p, P, I, ce, CE and loss lines from the logit bound e_z [M, K].  s_adds: the float32 additions that form s (the head's butterfly: at
-    most 5; a serial sum over K classes: K - 1), each worth half an ulp in r_k and in log s.  -> dict with dp [M, K], E_P, E_I, E_CE [K], sums, loss"""
+    most 5; a serial sum over K classes: K - 1), each worth half an ulp in r_k and in log s.  wc, wd: the weights `ref` was computed with.
+    -> dict with dp [M, K], E_P, E_I, E_CE [K], sums, loss"""
     cnt = ref["counted"].double().unsqueeze(1)
     g, p = ref["g"], ref["p"]
     emax = e_z.max(1, keepdim=True).values
@@ -118,24 +133,25 @@ def forward_bounds(e_z, ref, K, M, s_adds=5):
     Mc = ref["Mc"]
     t = dict(dp=dp, E_P=E_P, E_I=E_I, E_CE=E_CE)
     t["sums"] = torch.cat([torch.stack([E_I, E_P, torch.zeros(K, dtype=torch.float64), E_CE], dim=1).reshape(-1), torch.zeros(1, dtype=torch.float64)])
-    t["loss"] = (E_CE.sum() / Mc if Mc else 0.0) + (1.0 / (K - 1)) * (2 * E_I / Uk + num * E_P / Uk ** 2)[1:].sum() + 2 * ULP * ref["loss"].abs()
+    t["loss"] = (abs(wc) * E_CE.sum() / Mc if Mc else 0.0) + (abs(wd) / (K - 1)) * (2 * E_I / Uk + num * E_P / Uk ** 2)[1:].sum() + 2 * ULP * ref["loss"].abs()
     return t
 
 
-def _bounds(a, w, b, ref, K, N, S, dtype, dloss):
+def _bounds(a, w, b, ref, K, N, S, dtype, dloss, wc=1.0, wd=1.0):
+    """The module docstring's lines; `ref` is the reference computed with the same wc, wd."""
     cntb = ref["counted"]
     cnt = cntb.double().unsqueeze(1)
     A, W = torch.where(cntb.unsqueeze(1), a.double().abs(), torch.zeros(1, dtype=torch.float64)), w.double().abs()
     g, p = ref["g"], ref["p"]
     M = a.shape[0]
     e_z = (C + 8) * U * (A @ W.t()) + U * b.double().abs()
-    t = forward_bounds(e_z, ref, K, M)
+    t = forward_bounds(e_z, ref, K, M, wc=wc, wd=wd)
     dp, E_P, E_I = t["dp"], t["E_P"], t["E_I"]
     Uk, num = ref["P"] + ref["G"] + 1.0, 2 * ref["I"] + 1.0
     Mc = ref["Mc"]
     c = abs(dloss)
-    cA = c / Mc if Mc else 0.0
-    cd = c / (K - 1)
+    cA = c * abs(wc) / Mc if Mc else 0.0
+    cd = c * abs(wd) / (K - 1)
     e1, e0 = cd * 2 / Uk, cd * num / Uk ** 2
     de1, de0 = e1 * E_P / Uk, cd * (2 * E_I / Uk ** 2 + 2 * num * E_P / Uk ** 3)
     for v in (e1, e0, de1, de0):
@@ -164,13 +180,14 @@ def _check(got, ref, tol, K, worst, where):
         assert bool((err <= tol[name]).all()), f"{name}: error / bound = {ratio:.3f} {where}"
 
 
-@pytest.mark.parametrize("K", KS)
+@pytest.mark.parametrize("K", ALL_KS)
 @_DTYPES
 def test_head_and_loss_against_float64_restatement(dtype, K):
     worst = {}
-    for si, (N, sp) in enumerate(SHAPES):
+    shapes, labels = (SHAPES, LABELS) if K in KS else (REDUCED_SHAPES, REDUCED_LABELS)
+    for si, (N, sp) in enumerate(shapes):
         S = sp[0] * sp[1] * sp[2]
-        for li, kind in enumerate(LABELS):
+        for li, kind in enumerate(labels):
             a, w, b, lab = _inputs(N, sp, K, dtype, kind, seed=10000 * K + 100 * si + 10 * li + (dtype == torch.bfloat16))
             ref = reference(a, w, b, lab, DLOSS)
             got = _run(a, w, b, lab, N, sp, dtype)
@@ -184,10 +201,11 @@ def test_head_and_loss_against_float64_restatement(dtype, K):
     print(f"[seg_mc_head {dtype} K={K}] worst error / bound: " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
 
 
-@pytest.mark.parametrize("K", [9, 16])
+@pytest.mark.parametrize("K", [5, 9, 15, 16])
 @_DTYPES
 def test_capped_grid_where_a_lane_walks_several_voxels(dtype, K):
-    """S > 32768: the grid is capped at 1024 blocks, every lane takes more than one voxel (the prefetching loop) -- same bounds."""
+    """S > 32768: the grid is capped at 1024 blocks, every lane takes more than one voxel (the prefetching loop) -- same bounds.  One padded class count
+    per KP range (5 in 8, 9 and 15 in 16) and the maximum."""
     N, sp = 1, (3, 7, 1829)
     S = sp[0] * sp[1] * sp[2]
     a, w, b, lab = _inputs(N, sp, K, dtype, "mixed30", seed=77 + K)
@@ -210,9 +228,27 @@ def test_a_label_outside_the_classes_is_not_counted():
     r0, r1 = _run(a, w, b, off, N, sp, dtype), _run(a, w, b, bad, N, sp, dtype)
     for k in r0:
         assert torch.equal(_bits(r0[k]), _bits(r1[k])), k
+    # the labels a padded class would answer to: K (the first one), KP - 1 (the last one), 16 (past every KP) and 127 (the largest a byte carries)
+    for K in (3, 5, 9, 13):
+        KP = 4 if K <= 4 else 8 if K <= 8 else 16
+        for dtype in (torch.float32, torch.bfloat16):
+            a, w, b, lab = _inputs(N, sp, K, dtype, "mixed", seed=3 + K)
+            off = lab.clone()
+            off[::4] |= 0x80
+            ad, wdev, bdev = _act(a, N, sp), w.cuda(), b.cuda()
+            r0 = _run(a, w, b, off, N, sp, dtype)
+            e0 = ops.seg_mc_head_eval(ad, wdev, bdev, dtype, labels=off.cuda().view(N, *sp), want_mask=True)
+            for y in sorted({v for v in (K, KP - 1, 16, 127) if v >= K}):
+                bad = lab.clone()
+                bad[::4] = y
+                r1 = _run(a, w, b, bad, N, sp, dtype)
+                for k in r0:
+                    assert torch.equal(_bits(r0[k]), _bits(r1[k])), f"{k}: label {y} at K={K} {dtype}"
+                e1 = ops.seg_mc_head_eval(ad, wdev, bdev, dtype, labels=bad.cuda().view(N, *sp), want_mask=True)
+                assert torch.equal(e0[0], e1[0]) and torch.equal(e0[2], e1[2]) and torch.equal(e0[3], e1[3]), f"eval: label {y} at K={K} {dtype}"
 
 
-def _exact_inputs(N, sp, K, seed):
+def _exact_inputs(N, sp, K, seed, kind="mixed30"):
     g = torch.Generator().manual_seed(seed)
     M = N * sp[0] * sp[1] * sp[2]
     a = lattice((M, C), *FINER["x"], g)
@@ -223,27 +259,34 @@ def _exact_inputs(N, sp, K, seed):
     if K >= 3:                        # classes 1 and 2 are the same function: wherever they lead, 1 is predicted
         w[2], b[2] = w[1], b[1]
     assert_exactly_summable(a.abs() @ w.abs().t() + b.abs(), unit(FINER["x"][1], FINER["w"][1]), "seg mc head logits")
-    return a, w, b, _labels("mixed30", M, K, g)
+    return a, w, b, _labels(kind, M, K, g)
 
 
-@pytest.mark.parametrize("K", [2, 3, 9, 16])
+EVAL_CASES = [(1, (1, 1, 1), None, 1), (3, (1, 3, 7), [1, 0, 1], 2), (1, (1, 1, 257), [2], 3), (3, (5, 13, 21), [1, 5, 1], 2), (1, (1, 4099, 1), None, 1),
+              (3, (2, 5, 7), [1, 0, 1], 2)]
+REDUCED_EVAL_CASES = [(3, (1, 3, 7), [1, 0, 1], 2), (3, (2, 5, 7), [1, 0, 1], 2), (1, (1, 1, 257), [2], 3)]
+EVAL_FULL_KS = (2, 3, 9, 16)
+
+
+@pytest.mark.parametrize("K", ALL_KS)
 @_DTYPES
 def test_eval_counts_and_label_map_equal_the_reference_on_exactly_summable_operands(dtype, K):
-    for N, sp, ci, n_cases in [(1, (1, 1, 1), None, 1), (3, (1, 3, 7), [1, 0, 1], 2), (1, (1, 1, 257), [2], 3), (3, (5, 13, 21), [1, 5, 1], 2), (1, (1, 4099, 1), None, 1)]:
+    cases, kinds = (EVAL_CASES, ("mixed30",)) if K in EVAL_FULL_KS else (REDUCED_EVAL_CASES, REDUCED_LABELS)
+    for (N, sp, ci, n_cases), kind in [(c, k) for c in cases for k in kinds]:
         S = sp[0] * sp[1] * sp[2]
-        a, w, b, lab = _exact_inputs(N, sp, K, seed=31 * K + S)
+        a, w, b, lab = _exact_inputs(N, sp, K, seed=31 * K + S, kind=kind)
         ref = reference(a, w, b, lab, case_index=ci, n_cases=n_cases, S=S)
         tied = (ref["z"] == ref["z"].max(1, keepdim=True).values).sum(1) >= 2
         assert int(tied.sum()) > 0, "the case list must contain voxels whose maximum is shared by two classes"
-        if K >= 3 and S > 1:
+        if K >= 3 and S > 1 and kind == "mixed30":
             assert int((tied & (ref["pred"] >= 1) & ref["counted"]).sum()) > 0, "... and ties whose lowest class is not the background"
         cid = None if ci is None else torch.tensor(ci, dtype=torch.int32, device="cuda")
         counts = torch.zeros((n_cases, K, 3), dtype=torch.int64, device="cuda")
         out = ops.seg_mc_head_eval(_act(a.to(dtype), N, sp), w.float().cuda(), b.float().cuda(), dtype, labels=lab.cuda().view(N, *sp), case_index=cid,
                                    counts=counts, want_mask=True)
         torch.cuda.synchronize()
-        assert out[0] is counts and torch.equal(counts.cpu(), ref["counts"]), f"counts differ at N={N} spatial={sp} K={K}"
-        assert torch.equal(out[3].reshape(-1).cpu(), ref["labelmap"]), f"label map differs at N={N} spatial={sp} K={K}"
+        assert out[0] is counts and torch.equal(counts.cpu(), ref["counts"]), f"counts differ at N={N} spatial={sp} K={K} labels={kind}"
+        assert torch.equal(out[3].reshape(-1).cpu(), ref["labelmap"]), f"label map differs at N={N} spatial={sp} K={K} labels={kind}"
         assert torch.equal(out[2].cpu()[2:4 * K:4], ref["G"]) and float(out[2][4 * K]) == ref["Mc"]
         # a second call ADDS to the table
         ops.seg_mc_head_eval(_act(a.to(dtype), N, sp), w.float().cuda(), b.float().cuda(), dtype, labels=lab.cuda().view(N, *sp), case_index=cid, counts=counts)
@@ -263,10 +306,10 @@ def _bits(t):
     return t.contiguous().view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32 if t.dtype == torch.float32 else torch.int64)
 
 
-@pytest.mark.parametrize("K", KS)
+@pytest.mark.parametrize("K", ALL_KS)
 @_DTYPES
 def test_argmax_of_the_logits_is_the_eval_label_map(dtype, K):
-    for N, sp in [(3, (1, 3, 7)), (2, (3, 5, 7)), (1, (1, 4099, 1))]:
+    for N, sp in [(3, (1, 3, 7)), (2, (3, 5, 7)), (1, (1, 4099, 1)), (3, (2, 5, 7))] if K in KS else REDUCED_SHAPES:
         a, w, b, _ = _inputs(N, sp, K, dtype, "mixed", seed=40 + K)
         ad, wd_, bd = _act(a, N, sp), w.cuda(), b.cuda()
         z = ops.seg_mc_head_logits(ad, wd_, bd, dtype)
@@ -300,6 +343,27 @@ def test_logits_with_a_mirror_are_the_plain_logits_permuted_and_accumulate_as_st
         sc = plain.clone()
         ops.seg_mc_head_logits(ad, wd_, bd, dtype, out=sc, flip=flip, first=True, scale=1.0 / 3.0)
         assert torch.equal(_bits(sc), _bits(want * torch.tensor(1.0 / 3.0, device="cuda"))), f"first with a scale, flip {flip}"
+
+
+@pytest.mark.parametrize("K", [k for k in ALL_KS if k not in (2, 9, 16)])
+@_DTYPES
+def test_mirrored_and_accumulated_logits_at_the_other_class_counts(dtype, K):
+    """The accumulating store of every class count the test above leaves out: one sequence of passes with a z mirror (code 4), an x mirror and a
+    non-first pass, the last one scaled -- plain float32, restated on the device with torch (one add per pass, one multiply)."""
+    N, sp = 2, (3, 5, 7)
+    a, w, b, _ = _inputs(N, sp, K, dtype, "mixed", seed=50 + K)
+    ad, wd_, bd = _act(a, N, sp), w.cuda(), b.cuda()
+    plain = ops.seg_mc_head_logits(ad, wd_, bd, dtype)
+    zr = a.double() @ w.double().t() + b.double()
+    e_z = (C + 8) * U * (a.double().abs() @ w.double().abs().t()) + U * b.double().abs()
+    assert bool(((plain.cpu().double().reshape(-1, K) - zr).abs() <= e_z).all())
+    un = lambda code: plain.flip([d + 1 for d in range(3) if code >> d & 1]).contiguous() if code else plain      # noqa: E731
+    out = torch.full_like(plain, float("nan"))
+    ops.seg_mc_head_logits(ad, wd_, bd, dtype, out=out, flip=4, first=True)
+    assert torch.equal(_bits(out), _bits(un(4))), "a first pass with a z mirror"
+    ops.seg_mc_head_logits(ad, wd_, bd, dtype, out=out, flip=1, first=False)
+    ops.seg_mc_head_logits(ad, wd_, bd, dtype, out=out, flip=6, first=False, scale=1.0 / 3.0)
+    assert torch.equal(_bits(out), _bits(((un(4) + un(1)) + un(6)) * torch.tensor(1.0 / 3.0, device="cuda"))), "three passes, the last one scaled"
 
 
 @_DTYPES
@@ -383,18 +447,75 @@ def test_autograd_node_hands_over_the_raw_calls_gradients(dtype):
     from pcrlv2_amd import functions as Fn
     N, sp, K = 3, (2, 3, 7), 9
     a, w, b, lab = _inputs(N, sp, K, dtype, "mixed30", seed=11)
-    raw = _run(a, w, b, lab, N, sp, dtype, dloss=1.0)
-    ad = _act(a, N, sp).requires_grad_(True)
-    wp, bp = torch.nn.Parameter(w.cuda().view(K, C, 1, 1, 1)), torch.nn.Parameter(b.cuda())
-    mod = types.SimpleNamespace(compute_dtype=dtype, _pass_idx=1)
-    Fn.reset_parked()
-    loss, sums = Fn.SegSoftmaxHeadFn.apply(ad, wp, bp, lab.cuda().view(N, *sp), 1.0, 1.0, mod)
-    assert loss.requires_grad and not sums.requires_grad
-    loss.backward()
+    seen = []
+    for wc, wd in ((1.0, 1.0), (0.25, 2.0)):
+        raw = _run(a, w, b, lab, N, sp, dtype, dloss=1.0, wc=wc, wd=wd)
+        ad = _act(a, N, sp).requires_grad_(True)
+        wp, bp = torch.nn.Parameter(w.cuda().view(K, C, 1, 1, 1)), torch.nn.Parameter(b.cuda())
+        mod = types.SimpleNamespace(compute_dtype=dtype, _pass_idx=1)
+        Fn.reset_parked()
+        loss, sums = Fn.SegSoftmaxHeadFn.apply(ad, wp, bp, lab.cuda().view(N, *sp), wc, wd, mod)
+        assert loss.requires_grad and not sums.requires_grad
+        loss.backward()
+        torch.cuda.synchronize()
+        assert torch.equal(loss.detach().cpu(), raw["loss"]) and torch.equal(sums.cpu(), raw["sums"])
+        assert torch.equal(_bits(ad.grad.permute(0, 2, 3, 4, 1).reshape(-1, C).cpu()), _bits(raw["dx"]))
+        assert torch.equal(wp.grad.view(K, C).cpu(), raw["dw"]) and torch.equal(bp.grad.cpu(), raw["db"])
+        seen.append(raw)
+    assert not torch.equal(seen[0]["loss"], seen[1]["loss"]) and not torch.equal(seen[0]["dw"], seen[1]["dw"]), "the weights reach the loss and the gradients"
+
+
+def _gap(x, y, tol):
+    """Whether x and y differ by more than 100 x the bound somewhere: the weights under test are far from the ones they could be mistaken for."""
+    return bool(((x - y).abs() > 100 * tol).any())
+
+
+@pytest.mark.parametrize("K", [2, 5, 16])
+@_DTYPES
+def test_unequal_loss_weights_against_float64_restatement(dtype, K):
+    """wc and wd multiply the two loss terms in the second launch of the forward and are folded into cA, e1, e0 of the backward; at (1, 1) a swap, a
+    weight left out or one applied twice cannot be seen.  Bounds as above with the weights in them.  On top: the sums do not depend on the weights (bit for
+    bit); at (0, 0) everything is exactly zero; the eval entry point's loss is the forward's bit for bit.  The test is not vacuous: at (0.25, 2.0) the
+    REFERENCE's loss, dW and db are further than 100 x the bound from the references with the weights swapped and with unit weights."""
+    worst = {}
+    for si, (N, sp) in enumerate(WEIGHT_SHAPES):
+        S = sp[0] * sp[1] * sp[2]
+        a, w, b, lab = _inputs(N, sp, K, dtype, "mixed30", seed=20000 * K + 100 * si + (dtype == torch.bfloat16))
+        ad, wdev, bdev, ld = _act(a, N, sp), w.cuda(), b.cuda(), lab.cuda().view(N, *sp)
+        unit_sums = _run(a, w, b, lab, N, sp, dtype)["sums"]
+        for wc, wd in WEIGHTS:
+            where = f"at N={N} spatial={sp} K={K} wc={wc} wd={wd} {dtype}"
+            ref = reference(a, w, b, lab, DLOSS, wc, wd)
+            got = _run(a, w, b, lab, N, sp, dtype, wc=wc, wd=wd)
+            tol = _bounds(a, w, b, ref, K, N, S, dtype, DLOSS, wc, wd)
+            assert torch.equal(_bits(got["sums"]), _bits(unit_sums)), "the sums do not depend on the weights " + where
+            _check(got, ref, tol, K, worst, where)
+            if (wc, wd) == (0.0, 0.0):
+                assert float(got["loss"]) == 0.0 and not bool(got["dx"].float().abs().any()) and not bool(got["dw"].abs().any()) and not bool(got["db"].abs().any())
+            if (wc, wd) == (0.25, 2.0):
+                for other in (reference(a, w, b, lab, DLOSS, wd, wc), reference(a, w, b, lab, DLOSS, 1.0, 1.0)):
+                    for name in ("loss", "dw", "db"):
+                        assert _gap(ref[name], other[name], tol[name]), f"{name}: the reference does not tell these weights from others {where}"
+            out = ops.seg_mc_head_eval(ad, wdev, bdev, dtype, labels=ld, wc=wc, wd=wd)
+            torch.cuda.synchronize()
+            assert torch.equal(_bits(out[1].cpu()), _bits(got["loss"])) and torch.equal(_bits(out[2].cpu()), _bits(got["sums"])), "eval " + where
+    print(f"[seg_mc_head weights {dtype} K={K}] worst error / bound: " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
+
+
+@pytest.mark.parametrize("K", [3, 9])
+@_DTYPES
+def test_backward_without_dx_leaves_dw_and_db_as_they_are(dtype, K):
+    """need_dx=False hands the kernel a null dx: no dx comes back, dW and db are the bytes of the run that wrote one."""
+    N, sp = 3, (2, 5, 7)
+    a, w, b, lab = _inputs(N, sp, K, dtype, "mixed30", seed=13)
+    ad, wdev, bdev, ld = _act(a, N, sp), w.cuda(), b.cuda(), lab.cuda().view(N, *sp)
+    loss, sums = ops.seg_mc_head_forward(ad, wdev, bdev, ld, dtype)
+    dl = torch.tensor(DLOSS, device="cuda")
+    dx, dw, db = ops.seg_mc_head_backward(ad, wdev, bdev, ld, sums, dl, dtype)
+    none, dw2, db2 = ops.seg_mc_head_backward(ad, wdev, bdev, ld, sums, dl, dtype, need_dx=False)
     torch.cuda.synchronize()
-    assert torch.equal(loss.detach().cpu(), raw["loss"]) and torch.equal(sums.cpu(), raw["sums"])
-    assert torch.equal(_bits(ad.grad.permute(0, 2, 3, 4, 1).reshape(-1, C).cpu()), _bits(raw["dx"]))
-    assert torch.equal(wp.grad.view(K, C).cpu(), raw["dw"]) and torch.equal(bp.grad.cpu(), raw["db"])
+    assert none is None and dx is not None and bool(dw.abs().sum() > 0)
+    assert torch.equal(_bits(dw), _bits(dw2)) and torch.equal(_bits(db), _bits(db2))
 
 
 def test_label_map_groups_match_numpy():

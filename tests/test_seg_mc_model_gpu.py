@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from pcrlv2_amd import data_seg as D  # noqa: E402
 from pcrlv2_amd import functions as Fn, ops  # noqa: E402
 from pcrlv2_amd.models import PCRLv23d, Segmenter3d  # noqa: E402
+from pcrlv2_amd.train_seg import loss_from_sums  # noqa: E402
 from seg_mc_reference import lowest_argmax, reference  # noqa: E402
 from test_seg_mc_head_gpu import _bounds  # noqa: E402
 
@@ -74,6 +75,53 @@ def test_loss_is_the_reference_on_the_models_features_and_every_trainable_parame
         err = (g.double() - ref[name]).abs()
         print(f"[seg_mc model {dtype}] {name}: worst error / bound {float((err / tol[name].clamp_min(1e-300)).max()):.3f}")
         assert bool((err <= tol[name]).all()), name
+
+
+@_DTYPES
+def test_the_models_loss_weights_reach_the_training_loss_and_the_eval_loss(dtype):
+    """Segmenter3d(head='softmax', wc=0.5, wd=1.5): model.loss is the raw forward with THESE weights on the model's own features bit for bit and the
+    float64 restatement with them within tests/test_seg_mc_head_gpu.py's bound (a swap, or the defaults, is far outside it); infer's loss is
+    train_seg.loss_from_sums of infer's sums with the model's weights, to the float32 rounding of the device value (the device evaluates the same
+    float64 expression, possibly with one fused multiply-add: 8 x 2^-53 of the terms, then half a float32 ulp)."""
+    wc, wd = 0.5, 1.5
+    torch.manual_seed(0)
+    model = Segmenter3d(K, head="softmax", wc=wc, wd=wd).cuda().train().set_compute_dtype(dtype)
+    assert (model.wc, model.wd) == (wc, wd)
+    x, lab = _batch()
+    ops.begin_step()
+    Fn.reset_parked()
+    loss, sums = model.loss(x, lab)
+    loss.backward()
+    torch.cuda.synchronize()
+    ops.begin_step()
+    Fn.reset_parked()
+    with torch.no_grad():
+        a = ops.to_act(model.features(x), dtype)
+        ops.end_of_forward_join()
+    fc = model.out_tr.final_conv
+    l2, s2 = ops.seg_mc_head_forward(a, fc.weight, fc.bias, lab, dtype, wc, wd)
+    torch.cuda.synchronize()
+    assert torch.equal(l2.cpu(), loss.detach().cpu()) and torch.equal(s2.cpu(), sums.cpu())
+    rows, w, b = _rows(a), fc.weight.detach().view(K, 64).cpu(), fc.bias.detach().cpu()
+    flat = lab.cpu().reshape(-1)
+    ref = reference(rows, w, b, flat, 1.0, wc, wd)
+    tol = _bounds(rows, w, b, ref, K, B, CROP[0] * CROP[1] * CROP[2], dtype, 1.0, wc, wd)
+    for name, g in (("loss", loss.detach().cpu()), ("sums", sums.cpu())):
+        err = (g.double() - ref[name]).abs()
+        print(f"[seg_mc model weights {dtype}] {name}: worst error / bound {float((err / tol[name].clamp_min(1e-300)).max()):.3f}")
+        assert bool((err <= tol[name]).all()), name
+    for other in (reference(rows, w, b, flat, 1.0, wd, wc), reference(rows, w, b, flat, 1.0, 1.0, 1.0)):
+        assert float((ref["loss"] - other["loss"]).abs()) > 100 * float(tol["loss"]), "these weights are told from the swapped and the unit ones"
+    # the eval path
+    _, eloss, esums, _ = model.infer(x, labels=lab)
+    torch.cuda.synchronize()
+    host = esums.cpu().tolist()
+    want = loss_from_sums(host, K, wd=model.wd, head="softmax", wc=model.wc)
+    mc = host[4 * K]
+    terms = wc * sum(host[4 * k + 3] for k in range(K)) / mc + wd * 2.0
+    assert mc > 0 and abs(float(eloss) - want) <= 2.0 ** -24 * abs(want) + 8 * 2.0 ** -53 * terms
+    swapped, unit = loss_from_sums(host, K, wd=wc, head="softmax", wc=wd), loss_from_sums(host, K, head="softmax")
+    assert abs(want - swapped) > 100 * 2.0 ** -23 * abs(want) and abs(want - unit) > 100 * 2.0 ** -23 * abs(want)
 
 
 @_DTYPES

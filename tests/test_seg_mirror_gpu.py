@@ -154,6 +154,20 @@ def test_a_sequence_of_passes_equals_the_float32_restatement(dtype, K):
             assert runs[0] == want.tobytes(), f"N={N} crop={sp} codes {codes} scale {scale}"
 
 
+@pytest.mark.parametrize("K", [2, 4, 5, 6])
+@_DTYPES
+def test_a_sequence_of_passes_at_the_other_class_counts(dtype, K):
+    """The instantiations the two tests above leave out: one sequence with a z mirror (codes 4 and 7) and non-first passes, the last one scaled by
+    float32(1/3), on the smaller shape -- the same restatement, bit for bit."""
+    N, sp = HEAD_SHAPES[0]
+    acts, w, b = _head_inputs(N, sp, K, dtype, seed=7 * K + N)
+    plain = [ops.seg_head_logits(_ndhwc(a), w, b, dtype) for a in acts]
+    codes, scale = [4, 3, 7], np.float32(1 / 3)
+    want = tta_logits([flip_axes(plain[i % len(acts)], code, 1).cpu().numpy() for i, code in enumerate(codes)], scale)
+    z = torch.full(plain[0].shape, -7.0, dtype=torch.float32, device=DEV)
+    assert _bytes(_sequence(acts, w, b, dtype, codes, scale, z)) == want.tobytes(), f"N={N} crop={sp} codes {codes} K={K}"
+
+
 @_DTYPES
 def test_accumulating_head_refuses_bad_codes_grids_and_buffers(dtype):
     N, sp, K = 3, (3, 5, 7), 3

@@ -10,12 +10,15 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from pcrlv2_amd import data_seg as D  # noqa: E402
 from pcrlv2_amd import functions as Fn, ops  # noqa: E402
 from pcrlv2_amd.models import PCRLv23d, Segmenter3d  # noqa: E402
 from pcrlv2_amd.optim import FusedSGD  # noqa: E402
-from pcrlv2_amd.train_seg import train_step  # noqa: E402
+from pcrlv2_amd.train_seg import loss_from_sums, train_step  # noqa: E402
+from seg_reference import reference  # noqa: E402
+from test_seg_head_gpu import _bounds  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 K, B = 3, 2
@@ -137,6 +140,50 @@ def test_loss_backward_equals_the_seam_done_by_hand(dtype, crop):
             assert got is not None and torch.equal(_bits(got), _bits(first[n])), n
         else:
             assert got is None, n
+
+
+@_DTYPES
+def test_the_models_loss_weights_reach_the_training_loss_and_the_eval_loss(dtype):
+    """Segmenter3d(wb=0.25, wd=2.0): model.loss is the raw forward with THESE weights on the model's own features bit for bit and the float64
+    restatement with them within tests/test_seg_head_gpu.py's bound (a swap, or the defaults, is far outside it); infer's loss is
+    train_seg.loss_from_sums of infer's sums with the model's weights, to the float32 rounding of the device value (the device evaluates the same
+    float64 expression, possibly with one fused multiply-add: 8 x 2^-53 of the terms, then half a float32 ulp)."""
+    wb, wd, crop = 0.25, 2.0, CROPS[0]
+    torch.manual_seed(0)
+    model = Segmenter3d(K, wb=wb, wd=wd).cuda().train().set_compute_dtype(dtype)
+    assert (model.wb, model.wd) == (wb, wd)
+    x, lab = _batch(crop)
+    _fresh_step()
+    loss, sums = model.loss(x, lab)
+    loss.backward()
+    torch.cuda.synchronize()
+    _fresh_step()
+    with torch.no_grad():
+        a = ops.to_act(model.features(x), dtype)
+        ops.end_of_forward_join()
+    fc = model.out_tr.final_conv
+    l2, s2 = ops.seg_head_forward(a, fc.weight, fc.bias, lab, dtype, wb, wd)
+    torch.cuda.synchronize()
+    assert torch.equal(_bits(l2), _bits(loss)) and torch.equal(s2.cpu(), sums.cpu())
+    rows, w, b = a.detach().permute(0, 2, 3, 4, 1).reshape(-1, 64).cpu(), fc.weight.detach().view(K, 64).cpu(), fc.bias.detach().cpu()
+    flat = lab.cpu().reshape(-1)
+    ref = reference(rows, w, b, flat, 1.0, wb, wd)
+    tol = _bounds(rows, w, b, ref, K, B, crop[0] * crop[1] * crop[2], dtype, 1.0, wb, wd)
+    for name, g in (("loss", loss.detach().cpu()), ("sums", sums.cpu())):
+        err = (g.double() - ref[name]).abs()
+        print(f"[seg model weights {dtype}] {name}: worst error / bound {float((err / tol[name].clamp_min(1e-300)).max()):.3f}")
+        assert bool((err <= tol[name]).all()), name
+    for other in (reference(rows, w, b, flat, 1.0, wd, wb), reference(rows, w, b, flat, 1.0, 1.0, 1.0)):
+        assert float((ref["loss"] - other["loss"]).abs()) > 100 * float(tol["loss"]), "these weights are told from the swapped and the unit ones"
+    # the eval path
+    _, eloss, esums, _ = model.infer(x, labels=lab)
+    torch.cuda.synchronize()
+    host = esums.cpu().tolist()
+    want = loss_from_sums(host, K, model.wb, model.wd)
+    mc = host[4 * K]
+    terms = wb * sum(host[4 * k + 3] for k in range(K)) / (mc * K) + wd * 2.0
+    assert mc > 0 and abs(float(eloss) - want) <= 2.0 ** -24 * abs(want) + 8 * 2.0 ** -53 * terms
+    assert abs(want - loss_from_sums(host, K, wd, wb)) > 100 * 2.0 ** -23 * abs(want) and abs(want - loss_from_sums(host, K)) > 100 * 2.0 ** -23 * abs(want)
 
 
 @_CROPS
